@@ -9,6 +9,12 @@ sequence per rank (seed + rank), no collective in the data path ("scaling": "wea
 timed region rank 0 gathers each rank's per-frame (keypoints, matches) summary over RCCL.
 
 Launch: python bench.py [--gpus 1 --steps K --warmup W]; for N > 1 via torch.distributed.run.
+
+A plain run does what the headline figure needs and no more: set-up, warm-up, the K timed steps
+of the ORB leg, the result line.  --full adds every other leg and check (the per-kernel pass, the
+oracle parity of the last batch, rBRIEF-31, the pipelined rate, BA, pose-only BA, tracking, the CPU
+baselines), each still governed by its own --no-* switch.  --dump-outputs DIR writes what the last
+timed step computed as DIR/<name>.npy (last_step_outputs).
 """
 from __future__ import annotations
 
@@ -34,6 +40,11 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--full", action="store_true",
+                   help="also run every leg and check beyond the headline ORB steps (per-kernel pass, oracle parity, "
+                        "rBRIEF-31, pipelined rate, BA, pose-only BA, tracking, CPU baselines)")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="rank 0 writes the last timed step's outputs as DIR/<name>.npy (last_step_outputs)")
     p.add_argument("--batch", type=int, default=256, help="frames per step")
     p.add_argument("--frames", type=int, default=1024, help="resident sequence length per rank")
     p.add_argument("--width", type=int, default=1280)
@@ -73,7 +84,12 @@ def parse():
     p.add_argument("--rehearse-one-gpu", action="store_true",
                    help="multi-rank rehearsal on a one-GPU box: every rank on cuda:0, gloo collectives (the flow "
                         "of the C5 configuration; times are not a scaling measurement)")
-    return p.parse_args()
+    args = p.parse_args()
+    if not args.full:  # a plain run: the headline ORB leg alone
+        args.no_ba = args.no_pose = args.no_tracking = args.no_cpu_baseline = True
+        args.no_rbrief31 = args.no_all_cores = True
+        args.pipelined_streams = args.batch_parity = 0
+    return args
 
 
 def orb_bytes_per_frame(w, h, n):
@@ -282,7 +298,47 @@ def verify_orb_batch(args, batch_frames, ring, b, out, variant):
                     f"byte for byte; matches against frame j - 1 of the same batch"}
 
 
-def run_orb(args, rank, world, local_rank, torch, dist, variant=None):
+OUTPUT_SAMPLE_FRAMES = 32  # frames of the last batch whose records --dump-outputs writes
+OUTPUT_SAMPLE_SEED = 20240  # the sample is the same from run to run
+
+
+def last_step_outputs(args, ring, b, out):
+    """What the last timed step left for its caller, as float arrays (--dump-outputs): the keypoint
+    and match counts of all B frames, and of a fixed seeded sample of OUTPUT_SAMPLE_FRAMES frames
+    the keypoint records (x, y, size, angle, response, octave, class_id), the descriptors (one value
+    per byte) and the match records (query, train, image index, distance).  Records past a frame's
+    count are zero.  A frame's matches are against the frame before it (slot b: the previous batch's
+    last frame).  At the default sizes ~11 MB."""
+    import torch
+
+    from mageslam_amd._lib import DM_DTYPE, KP_DTYPE
+
+    B, N = args.batch, args.features
+    idx = np.sort(np.random.default_rng(OUTPUT_SAMPLE_SEED).choice(B, min(B, OUTPUT_SAMPLE_FRAMES), replace=False))
+    sel = torch.from_numpy(idx).to(ring["cnt"].device)
+    cnt = ring["cnt"][b + 1:b + B + 1].cpu().numpy()
+    nm = out["nm"][:B].cpu().numpy()
+    kp = ring["kp"][b + 1:b + B + 1][sel].cpu().numpy().view(KP_DTYPE).reshape(len(idx), N)
+    de = ring["desc"][b + 1:b + B + 1][sel].cpu().numpy()
+    mt = out["mt"][:B][sel].cpu().numpy().view(DM_DTYPE).reshape(len(idx), N)
+    kp_ok = np.arange(N)[None, :] < cnt[idx][:, None]
+    mt_ok = np.arange(N)[None, :] < nm[idx][:, None]
+
+    def fields(a, ok):
+        return np.where(ok[..., None], np.stack([a[f].astype(np.float32) for f in a.dtype.names], -1), np.float32(0))
+
+    return {"sample_frames": idx.astype(np.float64), "keypoint_counts": cnt.astype(np.float64),
+            "match_counts": nm.astype(np.float64), "keypoints": fields(kp, kp_ok),
+            "descriptors": np.where(kp_ok[..., None], de, 0).astype(np.float32), "matches": fields(mt, mt_ok)}
+
+
+def write_outputs(directory, arrays):
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
+def run_orb(args, rank, world, local_rank, torch, dist, variant=None, dump=False):
     from mageslam_amd import _lib, matcher, multigpu, orb, synth
 
     W, H, N, B = args.width, args.height, args.features, args.batch
@@ -374,12 +430,13 @@ def run_orb(args, rank, world, local_rank, torch, dist, variant=None):
     # the timed region on copies of the results)
     parity = verify_orb_batch(args, frames[(s_last * B) % F:(s_last * B) % F + B], ring, b_last,
                               outs[s_last % NSTR], variant) if rank == 0 and args.batch_parity > 0 else None
+    outputs = last_step_outputs(args, ring, b_last, outs[s_last % NSTR]) if dump and rank == 0 else None
     el_max = multigpu.max_over_ranks(el, dev, dist)
     # end-of-run exchange (RCCL over xGMI): per-frame (keypoints, matches) of the last batch
     summary = torch.stack([cnt[1:].to(torch.int64), nm.to(torch.int64)], 1)
     gathered = multigpu.gather_rows(summary, dist)
     kern = {}
-    if args.profile:
+    if args.profile and args.full:
         lib.mage_profile_reset()
         lib.mage_profile_enable(1)
         for s in range(args.warmup + args.steps, args.warmup + 2 * args.steps):
@@ -392,14 +449,18 @@ def run_orb(args, rank, world, local_rank, torch, dist, variant=None):
         "value": frames_total / el_max,
         "ms_per_step": 1000.0 * el_max / args.steps,
         "frames_per_step": B,
-        "kernels": {k: {"launches": c, "avg_ms": ms / max(c, 1)} for k, (c, ms) in kern.items()},
+        "kernels": {k: {"launches": c, "avg_ms": ms / max(c, 1)} for k, (c, ms) in (kern if args.full else kern_timed).items()},
         "kernel_timing": "dispatch timestamps of one more pass of the same steps after the timed region "
-                         "(the timed region times the roofline kernel only)",
+                         "(the timed region times the roofline kernel only)" if args.full else
+                         "dispatch timestamps of the roofline kernel in the timed region (--full: every kernel, in one "
+                         "more pass of the same steps)",
         "mean_keypoints": float(torch.cat(gathered)[:, 0].float().mean().item()),
         "mean_matches": float(torch.cat(gathered)[:, 1].float().mean().item()),
     }
     if parity is not None:
         res["parity"] = parity
+    if outputs is not None:
+        res["outputs"] = outputs
     orb_k = {k: {"launches": c, "avg_ms": ms / max(c, 1)} for k, (c, ms) in kern_timed.items()}
     if orb_k:
         dom = ROOF_KERNEL
@@ -1131,7 +1192,10 @@ def main():
     dist = multigpu.init("gloo" if args.rehearse_one_gpu else "nccl", local_rank)
 
     orb_res = run_orb(args, rank, world, local_rank, torch, dist,
-                      variant=None if args.orb_variant == "c2" else args.orb_variant)
+                      variant=None if args.orb_variant == "c2" else args.orb_variant, dump=bool(args.dump_outputs))
+    outputs = orb_res.pop("outputs", None)
+    if outputs is not None:
+        write_outputs(args.dump_outputs, outputs)
     r31_res = None
     if world == 1 and not args.no_rbrief31 and args.orb_variant == "c2":
         import copy
@@ -1170,6 +1234,7 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": orb_res["ms_per_step"],
+            "full": args.full,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,

@@ -1,5 +1,5 @@
 """bench.py against a variant library built by tools/abl.py (development tool, not the product):
-python tools/abl_bench.py <variant> [bench.py arguments...]"""
+python tools/abl_bench.py <variant> [bench.py arguments...]   (--full among them for the legs beyond the headline)"""
 import ctypes as C
 import runpy
 import sys

@@ -23,9 +23,9 @@ run_set() {  # <out dir> <command...>
 OUT=gpurun_out/prof_$TAG
 ORB=gpurun_out/prof_${TAG}_orb
 ROWS=gpurun_out/prof_${TAG}_rows
-ORB_CMD="python3 bench.py --steps 10 --warmup 3 --no-ba --no-pose --no-tracking --no-cpu-baseline --pipelined-streams 0 --no-all-cores --no-rbrief31"
+ORB_CMD="python3 bench.py --full --steps 10 --warmup 3 --no-ba --no-pose --no-tracking --no-cpu-baseline --pipelined-streams 0 --no-all-cores --no-rbrief31"
 ORB31=gpurun_out/prof_${TAG}_orb31
-ORB31_CMD="python3 bench.py --steps 10 --warmup 3 --no-ba --no-pose --no-tracking --no-cpu-baseline --pipelined-streams 0 --no-all-cores --orb-variant rbrief31"
+ORB31_CMD="python3 bench.py --full --steps 10 --warmup 3 --no-ba --no-pose --no-tracking --no-cpu-baseline --pipelined-streams 0 --no-all-cores --orb-variant rbrief31"
 if [ "$2" = collect ]; then
   if [ -d $OUT/trace ]; then
     python3 tools/rocprof_summary.py $OUT $TAG "python bench.py" 3 > /dev/null
@@ -55,7 +55,7 @@ fi
 #   main = headline + ORB-only sets, rows = the per-row set + the final default bench line
 PHASE=${2:-all}
 if [ "$PHASE" = all ] || [ "$PHASE" = main ]; then
-    run_set $OUT python3 bench.py --steps 10 --warmup 3 --ba-iters 20 --no-cpu-baseline --pipelined-streams 0 --no-all-cores --no-tracking --no-rbrief31
+    run_set $OUT python3 bench.py --full --steps 10 --warmup 3 --ba-iters 20 --no-cpu-baseline --pipelined-streams 0 --no-all-cores --no-tracking --no-rbrief31
     run_set $ORB $ORB_CMD
     run_set $ORB31 $ORB31_CMD
 fi
@@ -66,5 +66,5 @@ fi
 if [ "$PHASE" = all ] || [ "$PHASE" = rows ]; then
     run_set $ROWS python3 tools/bench_rows.py
     mkdir -p $OUT
-    timeout -k 10 600 python3 bench.py > $OUT/bench_final.json 2> $OUT/bench_final.err
+    timeout -k 10 600 python3 bench.py --full > $OUT/bench_final.json 2> $OUT/bench_final.err
 fi

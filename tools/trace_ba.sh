@@ -8,6 +8,6 @@ cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
 mkdir -p gpurun_out/batrace
 timeout -k 10 200 rocprofv3 --kernel-trace --memory-copy-trace -d gpurun_out/batrace/t -o run --output-format csv \
-    -- python3 bench.py --steps 2 --warmup 1 --no-pose --no-tracking --no-cpu-baseline --no-all-cores \
+    -- python3 bench.py --full --steps 2 --warmup 1 --no-pose --no-tracking --no-cpu-baseline --no-all-cores \
     --pipelined-streams 0 --profile 0 > gpurun_out/batrace/out.log 2>&1
 find gpurun_out/batrace -name '*.csv' -exec gzip -f {} \;
