@@ -195,6 +195,99 @@ inline unsigned IndexedMatch(const OnlineBowTree& tree, const std::vector<Descri
     return n;
 }
 
+// NewMapPointsCreationSettings (MageSettings.h:55-61) with CameraSettings' new-point grid
+// (MageSettings.h:311-313) and the pyramid and image size of Ki.
+struct NewMapPointsCreationSettings {
+    float MinParallaxDegrees{0.0238961594253207f};
+    float MaxEpipolarError{3.84385518580709f};
+    float MinAcceptedDistanceRatio{2.0f};
+    unsigned NewPointGridWidth{4}, NewPointGridHeight{3}, NewPointMaxGridCount{6};
+    float PyramidScale{1.2f};
+    unsigned NumLevels{8};
+    unsigned ImageWidth{1280}, ImageHeight{720};
+};
+
+// What CreateInitialAssociations reads of a keyframe: Pose as view-space t and column-major R (the
+// layout BundlerLib::SetCameraPose takes), the undistorted calibration {cx, cy, fx, fy}, the keypoints.
+struct KeyframeView {
+    std::array<float, 3> Position;
+    std::array<float, 9> Rotation;
+    std::array<float, 4> Intrinsics;
+    const std::vector<KeyPoint>* KeyPoints;
+};
+
+using NewMapPoint = mage_new_point;
+
+// CreateInitialAssociations' match loop (Mapping/NewMapPointsCreation.cpp:187-201, 277-321, with
+// TryCreateNewAssociatedMapPointForMatch, :74-160): the matches of each covisible keyframe (in the
+// order the reference visits them; queryIdx = Kc keypoint, trainIdx = Ki keypoint) against Ki.
+// Returns the new points in the reference's push_back order; `verdicts`, when given, gets one
+// MAGE_NP_* code per match and keyframe.  device < 0 runs the CPU backend.
+inline std::vector<NewMapPoint> CreateInitialAssociations(const NewMapPointsCreationSettings& settings,
+                                                          const KeyframeView& Ki,
+                                                          const std::vector<bool>& KiAssociatedKeypointMask,
+                                                          const std::vector<KeyframeView>& covisibleKeyframes,
+                                                          const std::vector<std::vector<DMatch>>& matches,
+                                                          std::vector<std::vector<uint8_t>>* verdicts = nullptr,
+                                                          int device = 0)
+{
+    if (matches.size() != covisibleKeyframes.size())
+        throw std::invalid_argument("one match list per covisible keyframe");
+    mage_new_points_settings s{};
+    s.struct_size = (uint32_t)sizeof(s);
+    s.max_epipolar_error = settings.MaxEpipolarError;
+    s.min_accepted_distance_ratio = settings.MinAcceptedDistanceRatio;
+    s.min_parallax_degrees = settings.MinParallaxDegrees;
+    s.pyramid_scale = settings.PyramidScale;
+    s.num_levels = settings.NumLevels;
+    s.grid_width = settings.NewPointGridWidth;
+    s.grid_height = settings.NewPointGridHeight;
+    s.max_grid_count = settings.NewPointMaxGridCount;
+    s.image_width = settings.ImageWidth;
+    s.image_height = settings.ImageHeight;
+    const uint32_t n_kc = (uint32_t)covisibleKeyframes.size();
+    std::vector<float> pos, rot, intr;
+    std::vector<KeyPoint> kps;
+    std::vector<DMatch> all;
+    std::vector<uint32_t> kp_start(n_kc + 1, 0), m_start(n_kc + 1, 0);
+    for (uint32_t k = 0; k < n_kc; k++) {
+        const KeyframeView& kc = covisibleKeyframes[k];
+        pos.insert(pos.end(), kc.Position.begin(), kc.Position.end());
+        rot.insert(rot.end(), kc.Rotation.begin(), kc.Rotation.end());
+        intr.insert(intr.end(), kc.Intrinsics.begin(), kc.Intrinsics.end());
+        kps.insert(kps.end(), kc.KeyPoints->begin(), kc.KeyPoints->end());
+        all.insert(all.end(), matches[k].begin(), matches[k].end());
+        kp_start[k + 1] = (uint32_t)kps.size();
+        m_start[k + 1] = (uint32_t)all.size();
+    }
+    std::vector<uint8_t> mask(KiAssociatedKeypointMask.begin(), KiAssociatedKeypointMask.end());
+    if (!mask.empty() && mask.size() != Ki.KeyPoints->size())
+        throw std::invalid_argument("KiAssociatedKeypointMask must have one entry per Ki keypoint");
+    std::vector<NewMapPoint> out(std::max<size_t>(all.size(), 1));
+    std::vector<uint8_t> verdict(std::max<size_t>(all.size(), 1), 0xFF);
+    uint32_t n = 0, status = 0;
+    const uint32_t n_ki = (uint32_t)Ki.KeyPoints->size();
+    const uint8_t* pm = mask.empty() ? nullptr : mask.data();
+    if (device < 0)
+        check(mage_new_map_points_host(&s, Ki.Position.data(), Ki.Rotation.data(), Ki.Intrinsics.data(),
+                                       Ki.KeyPoints->data(), n_ki, pm, n_kc, pos.data(), rot.data(), intr.data(),
+                                       kps.data(), kp_start.data(), all.data(), m_start.data(), out.data(),
+                                       (uint32_t)out.size(), &n, verdict.data(), &status));
+    else
+        check(mage_new_map_points(&s, Ki.Position.data(), Ki.Rotation.data(), Ki.Intrinsics.data(), Ki.KeyPoints->data(),
+                                  n_ki, pm, n_kc, pos.data(), rot.data(), intr.data(), kps.data(), kp_start.data(),
+                                  all.data(), m_start.data(), out.data(), (uint32_t)out.size(), &n, verdict.data(),
+                                  &status, device));
+    if (status & 1u) throw Error(MAGE_EUNSUPPORTED, "more than 4096 keypoints in Ki");
+    out.resize(n);
+    if (verdicts) {
+        verdicts->assign(n_kc, {});
+        for (uint32_t k = 0; k < n_kc; k++)
+            (*verdicts)[k].assign(verdict.begin() + m_start[k], verdict.begin() + m_start[k + 1]);
+    }
+    return out;
+}
+
 struct BundlerParameters {
     bool ArePointsFixed{false};
 };

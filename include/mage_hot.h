@@ -368,6 +368,100 @@ mage_status mage_indexed_match_batch_device(const uint8_t* d_desc_a, const uint3
                                             uint32_t* d_status, mage_stream stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* New map points — replaces NewMapPointsCreation's CreateInitialAssociations                  */
+/* (Core/.../Source/Mapping/NewMapPointsCreation.cpp)                                          */
+/* ------------------------------------------------------------------------------------------ */
+
+/* NewMapPointsCreationSettings (MageSettings.h:55-61), the pyramid of Ki, and the grid cap of
+ * CameraSettings (MageSettings.h:311-313).  struct_size must be sizeof(mage_new_points_settings);
+ * anything else is MAGE_EINVAL. */
+typedef struct mage_new_points_settings {
+    uint32_t struct_size;
+    float max_epipolar_error;          /* 3.84385518580709 (pixels) */
+    float min_accepted_distance_ratio; /* 2.0 */
+    float min_parallax_degrees;        /* 0.0238961594253207 */
+    float pyramid_scale;               /* Ki's pyramid scale factor (> 1) */
+    uint32_t num_levels;               /* Ki's pyramid levels, 1..MAGE_MAX_LEVELS */
+    uint32_t grid_width;               /* NewPointGridWidth 4 */
+    uint32_t grid_height;              /* NewPointGridHeight 3 (at most 64 cells) */
+    uint32_t max_grid_count;           /* NewPointMaxGridCount 6 */
+    uint32_t image_width, image_height;
+} mage_new_points_settings;
+
+/* One created map point, in the order of the reference's newMapPoints.push_back (:156): position,
+ * proxy::ViewingData {mean view direction, dMin, dMax} and the two associations (Ki keypoint; Kc
+ * slot and keypoint), plus the match's index within its slot.  48 bytes. */
+typedef struct mage_new_point {
+    float position[3];
+    float mean_view_dir[3];
+    float d_min, d_max;
+    uint32_t ki_index, kc_slot, kc_index, match_index;
+} mage_new_point;
+
+/* Verdict of a match: the reference's first reason to drop it, in the reference's order. */
+#define MAGE_NP_ACCEPTED 0
+#define MAGE_NP_EPIPOLAR 1       /* both epipolar distances sum over 2 * MaxEpipolarError (:82-88) */
+#define MAGE_NP_BEHIND 2         /* VerifyProjectInFront of Ki, then Kc (:96-100) */
+#define MAGE_NP_DISTANCE_RATIO 3 /* |X - Ci| / |Ci - Cc| < MinAcceptedDistanceRatio (:117-123) */
+#define MAGE_NP_SCALE 4          /* predicted octave differs from the Kc keypoint's (:126-130) */
+#define MAGE_NP_PARALLAX 5       /* cos of the two viewing directions > CosMinParallax (:137) */
+#define MAGE_NP_GRID_FULL 6      /* the Ki keypoint's grid cell is full at the match's turn (:301) */
+#define MAGE_NP_KI_TAKEN 7       /* an earlier match made a point of this Ki keypoint (:309) */
+#define MAGE_NP_BAD_INDEX 8      /* queryIdx / trainIdx or a keypoint octave out of range: nothing read */
+
+/* CreateInitialAssociations' loop over the matches of up to 8 covisible keyframes Kc against the new
+ * keyframe Ki (NewMapPointsCreation.cpp:171-329 from the grid counts on; the per-match geometry is
+ * TryCreateNewAssociatedMapPointForMatch, :74-160, with ComputeFundamentalMatrix, Utils/Epipolar.cpp:
+ * 14-48, DistanceFromEpipolarLine, :94-107, TriangulatePointWorldSpace, Tracking/Triangulation.cpp:
+ * 24-60, and ComputeOctave / ComputeDMin / ComputeDMax, Map/MappingMath.h:13-40).  Poses as
+ * mage_ba_set_cameras takes them: pos3 the view-space t, r9 the column-major R, intr4 {cx, cy, fx,
+ * fy}.  ki_associated (n_ki bytes, NULL = none) is Ki's associated-keypoint mask, which seeds the
+ * grid counts (:187-201).  The Kc slots are in processing order; their keypoints and their matches
+ * (queryIdx = Kc keypoint, trainIdx = Ki keypoint, as IndexedMatch(Kc, Ki) returns them) are
+ * concatenated, slot k owning [start[k], start[k + 1]).  verdict gets one MAGE_NP_* per match;
+ * accepted points go to out[0 .. min(*n_out, cap)) in processing order.  *status: bit 0 when n_ki
+ * exceeds 4096 (no points, verdicts untouched), bit 1 when more than cap points were accepted
+ * (*n_out is then cap).  More than 8 slots, more than 8 levels or more than 64 grid cells is
+ * MAGE_EINVAL.  Host buffers, synchronous, runs on `device`. */
+mage_status mage_new_map_points(const mage_new_points_settings* settings, const float* ki_pos3, const float* ki_r9,
+                                const float* ki_intr4, const mage_keypoint* ki_kp, uint32_t n_ki,
+                                const uint8_t* ki_associated, uint32_t n_kc, const float* kc_pos3, const float* kc_r9,
+                                const float* kc_intr4, const mage_keypoint* kc_kp, const uint32_t* kc_kp_start,
+                                const mage_dmatch* matches, const uint32_t* match_start, mage_new_point* out,
+                                uint32_t cap, uint32_t* n_out, uint8_t* verdict, uint32_t* status, int device);
+
+/* The same in plain C++ on the calling thread, with the reference's sequential loop (:290-321)
+ * over the same per-match arithmetic: the CPU backend, bit-identical to the kernel.  No GPU. */
+mage_status mage_new_map_points_host(const mage_new_points_settings* settings, const float* ki_pos3,
+                                     const float* ki_r9, const float* ki_intr4, const mage_keypoint* ki_kp,
+                                     uint32_t n_ki, const uint8_t* ki_associated, uint32_t n_kc, const float* kc_pos3,
+                                     const float* kc_r9, const float* kc_intr4, const mage_keypoint* kc_kp,
+                                     const uint32_t* kc_kp_start, const mage_dmatch* matches,
+                                     const uint32_t* match_start, mage_new_point* out, uint32_t cap, uint32_t* n_out,
+                                     uint8_t* verdict, uint32_t* status);
+
+/* Batched device form, one workgroup per problem (one Ki with d_n_kc[problem] <= kc_slots <= 8 Kc
+ * slots); pair = problem * kc_slots + slot.  Ki arrays advance per problem (poses 3 / 9 / 4 floats,
+ * keypoints and the optional associated mask ki_pitch entries, count d_n_ki[problem]); Kc arrays
+ * advance per pair (keypoints kc_pitch entries, count d_n_kc_kp[pair]).  The matches are read in
+ * the layout mage_indexed_match_batch_device writes with A = Kc and B = Ki: d_matches + pair *
+ * match_cap, count d_n_matches[pair] (a count over match_cap reads match_cap), so the two launches
+ * chain on one stream.  Verdicts at d_verdict + pair * match_cap, points at d_out + problem * cap,
+ * count in d_n_out[problem].  Bits of *d_status as above; bit 0 also for a problem with more than
+ * kc_slots slots or a Kc keypoint count over kc_pitch (that problem reports 0 points).
+ * Asynchronous on `stream`. */
+mage_status mage_new_map_points_batch_device(const mage_new_points_settings* settings, uint32_t problems,
+                                             uint32_t kc_slots, const float* d_ki_pos3, const float* d_ki_r9,
+                                             const float* d_ki_intr4, const mage_keypoint* d_ki_kp, int64_t ki_pitch,
+                                             const uint32_t* d_n_ki, const uint8_t* d_ki_associated,
+                                             const uint32_t* d_n_kc, const float* d_kc_pos3, const float* d_kc_r9,
+                                             const float* d_kc_intr4, const mage_keypoint* d_kc_kp, int64_t kc_pitch,
+                                             const uint32_t* d_n_kc_kp, const mage_dmatch* d_matches,
+                                             uint32_t match_cap, const uint32_t* d_n_matches, mage_new_point* d_out,
+                                             uint32_t cap, uint32_t* d_n_out, uint8_t* d_verdict, uint32_t* d_status,
+                                             mage_stream stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Local bundle adjustment — replaces BundlerLib (Dependencies/BundlerLib/Include/BundlerLib.h) */
 /* ------------------------------------------------------------------------------------------ */
 

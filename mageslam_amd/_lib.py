@@ -37,6 +37,7 @@ EXPORTS = [
     "mage_ba_set_tethers", "mage_ba_step", "mage_ba_get_poses", "mage_ba_get_points",
     "mage_ba_get_stats", "mage_ba_get_state_f64", "mage_ba_pose_batch", "mage_ba_pose_batch_device",
     "mage_track_sequence", "mage_track_sequence_device",
+    "mage_new_map_points", "mage_new_map_points_host", "mage_new_map_points_batch_device",
 ]
 
 
@@ -109,6 +110,19 @@ class TrackSettingsC(C.Structure):
                 ("map_point_depth_noise", C.c_float)]
 
 
+class NewPointsSettingsC(C.Structure):
+    """mage_new_points_settings (include/mage_hot.h); struct_size is filled in by make()."""
+    _fields_ = [("struct_size", C.c_uint32), ("max_epipolar_error", C.c_float),
+                ("min_accepted_distance_ratio", C.c_float), ("min_parallax_degrees", C.c_float),
+                ("pyramid_scale", C.c_float), ("num_levels", C.c_uint32), ("grid_width", C.c_uint32),
+                ("grid_height", C.c_uint32), ("max_grid_count", C.c_uint32), ("image_width", C.c_uint32),
+                ("image_height", C.c_uint32)]
+
+    @classmethod
+    def make(cls, **kw):
+        return cls(struct_size=C.sizeof(cls), **kw)
+
+
 class BAStats(C.Structure):
     _fields_ = [("iterations", C.c_uint64), ("trials", C.c_uint64), ("rejected_trials", C.c_uint64),
                 ("last_chi2", C.c_double), ("lambda_", C.c_double)]
@@ -118,6 +132,9 @@ KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4
                      ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
 DM_DTYPE = np.dtype([("query_idx", "<i4"), ("train_idx", "<i4"), ("img_idx", "<i4"),
                      ("distance", "<f4")])
+# mage_new_point (48 B)
+NP_DTYPE = np.dtype([("position", "<f4", 3), ("mean_view_dir", "<f4", 3), ("d_min", "<f4"), ("d_max", "<f4"),
+                     ("ki_index", "<u4"), ("kc_slot", "<u4"), ("kc_index", "<u4"), ("match_index", "<u4")])
 
 _lib = None
 
@@ -234,3 +251,9 @@ def _declare(L: C.CDLL) -> None:
     sig("mage_track_sequence_device", st, vp, vp, u32, vp, u32, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp, vp)
     sig("mage_ba_pose_batch", st, u32, vp, vp, vp, vp, vp, vp, vp, u32, f32, f32, vp, vp, vp, vp, vp, vp, C.c_int)
     sig("mage_ba_pose_batch_device", st, u32, vp, vp, vp, vp, vp, vp, vp, u32, f32, f32, vp, vp, vp, vp, vp, vp, vp)
+    sig("mage_new_map_points", st, vp, vp, vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, vp,
+        C.c_int)
+    sig("mage_new_map_points_host", st, vp, vp, vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp,
+        vp)
+    sig("mage_new_map_points_batch_device", st, vp, u32, u32, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp,
+        vp, u32, vp, vp, u32, vp, vp, vp, vp)
