@@ -155,6 +155,14 @@ mage_status mage_orb_fast_score_map(const uint8_t* img, int32_t width, int32_t h
                                     int32_t stride, int32_t threshold, uint8_t* score_map,
                                     int device);
 
+/* Debug view of how the FAST kernels stage tile (tx, ty) (120 x 30 outputs, a 136 x 38 window from
+ * (120 tx - 8, 30 ty - 4), reflect-101 outside the frame) of a width x height frame: runs on the host,
+ * no device.  *path = 0 generic per-dword loop, 1 interior, 2 border.  For 1 and 2, loads holds
+ * 38 x 9 pairs {byte offset in the frame, bytes loaded} (tile row major, 9 chunks per row) and, when
+ * img is given, tile (38 x 136 bytes) is the window assembled from img by exactly those loads. */
+mage_status mage_debug_fast_tile_plan(const uint8_t* img, int32_t width, int32_t height, int32_t stride,
+                                      int32_t tx, int32_t ty, int32_t* path, int32_t* loads, uint8_t* tile);
+
 /* Camera calibration as OrbFeatureDetector::Process receives it (Device/CameraCalibration.h):
  * the linear intrinsics of GetCameraMatrix() and the OpenCV-ordered distortion coefficients of
  * GetCVDistortionCoeffs() — K1 K2 P1 P2 K3 (Poly3k, ndist = 5) [K4 K5 K6] (Rational6k, ndist = 8);

@@ -24,6 +24,7 @@ EXPORTS = [
     "mage_orb_detect_and_compute_batch_device", "mage_orb_status", "mage_orb_reset_status",
     "mage_orb_set_fast_gate", "mage_orb_fast_gate_stats",
     "mage_synth_frames_device", "mage_synth_scene_device", "mage_orb_fast_score_map",
+    "mage_debug_fast_tile_plan",
     "mage_undistort_keypoints", "mage_undistort_keypoints_batch_device",
     "mage_undistorter_create", "mage_undistorter_destroy", "mage_undistorter_get_maps", "mage_undistort_image",
     "mage_undistort_image_batch_device", "mage_resize_linear_device", "mage_scale_for_camera_configuration",
@@ -205,6 +206,7 @@ def _declare(L: C.CDLL) -> None:
     f64 = C.c_double
     sig("mage_synth_scene_device", st, vp, u32, i32, i32, i64, vp, f64, f64, f64, f64, f64, f64, i64, u64, vp)
     sig("mage_orb_fast_score_map", st, vp, i32, i32, i32, i32, vp, C.c_int)
+    sig("mage_debug_fast_tile_plan", st, vp, i32, i32, i32, i32, i32, vp, vp, vp)
     sig("mage_undistort_keypoints", st, vp, vp, vp, u32, C.c_int)
     sig("mage_undistort_keypoints_batch_device", st, vp, vp, vp, i64, vp, u32, vp)
     sig("mage_undistorter_create", st, vp, i32, i32, C.c_int, C.POINTER(vp), vp)

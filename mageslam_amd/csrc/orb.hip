@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "fast_tile_plan.hpp"
 #include "lds_sort.hpp"
 #include "orb_tables.hpp"
 
@@ -210,6 +211,125 @@ __device__ __forceinline__ int reflect101(int i, int n)
     return i;
 }
 
+// 16 bytes (byte j = bits 8 (j & 3) of dword j >> 2) shifted down by s bytes, 0 <= s <= 15, zero filled
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ u32x4 shr_bytes(u32x4 a, int s)
+{
+    if (s & 8) a = u32x4{a[2], a[3], 0u, 0u};
+    if (s & 4) a = u32x4{a[1], a[2], a[3], 0u};
+    const uint32_t b = (uint32_t)s & 3u;
+    return u32x4{__builtin_amdgcn_alignbyte(a[1], a[0], b), __builtin_amdgcn_alignbyte(a[2], a[1], b),
+                 __builtin_amdgcn_alignbyte(a[3], a[2], b), __builtin_amdgcn_alignbyte(0u, a[3], b)};
+}
+// the 16 bytes in reverse order
+__device__ __forceinline__ u32x4 rev_bytes(u32x4 a)
+{
+    return u32x4{__builtin_bswap32(a[3]), __builtin_bswap32(a[2]), __builtin_bswap32(a[1]), __builtin_bswap32(a[0])};
+}
+
+// load_tile's border path: a tile that needs one reflection at most per axis (tileplan::border_ok).
+// Out of line: inlined into fast_nms_kernel it costs the kernel's other paths a spill slot.
+__device__ __noinline__ void load_tile_border(const uint8_t* __restrict__ src_, int w_, int h_, int stride_,
+                                              uint8_t (*img)[LW], int gx0_, int gy0_)
+{
+    // arguments arrive in vector registers: back to scalars, they are uniform over the workgroup
+    const int w = __builtin_amdgcn_readfirstlane(w_), h = __builtin_amdgcn_readfirstlane(h_);
+    const int stride = __builtin_amdgcn_readfirstlane(stride_);
+    const int gx0 = __builtin_amdgcn_readfirstlane(gx0_), gy0 = __builtin_amdgcn_readfirstlane(gy0_);
+    const unsigned long long sa = (unsigned long long)src_;
+    const unsigned long long sb = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(sa >> 32)) << 32) |
+                                  (uint32_t)__builtin_amdgcn_readfirstlane((int)sa);
+    // loads of any alignment from the global address space (out of line, loads through a generic
+    // pointer are flat loads, which wait for one another)
+    typedef const __attribute__((address_space(1))) uint8_t* gptr;
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    typedef const __attribute__((address_space(1))) u32x2 __attribute__((aligned(1))) g_u2;
+    typedef const __attribute__((address_space(1))) u32x4 __attribute__((aligned(1))) g_u4;
+    const gptr src = (gptr)sb;
+    // border tile, one reflection at most per axis: the interior mapping (chunk c of rows r0,
+    // r0 + 14, r0 + 28), one load per row, all in flight before the first LDS write.  A row
+    // outside the frame is its mirror row; a chunk's bytes come from inside the frame row by
+    // tileplan::chunk_plan: as they are, byte-reversed (right of the frame), or for the chunk the
+    // frame's edge cuts, picked from the row's first / last 16 bytes.  No load leaves [0, w).
+    static_assert(LW == tileplan::kLW && LH == tileplan::kLH, "the plan's tile window");
+    constexpr int RSTEP = FAST_THREADS / 9, NPASS = (LH + RSTEP - 1) / RSTEP;
+    const int c = threadIdx.x % 9, r0 = threadIdx.x / 9;
+    if (r0 >= RSTEP) return;
+    if (gx0 + LW <= w) {
+        // top, bottom and left tiles (no chunk reaches the frame's right edge): the interior path
+        // with mirrored rows, every chunk CHUNK_FULL but chunk 0 of a left tile (CHUNK_LEFT, the
+        // row's first 16 bytes); a wave pays for every instruction here, so the general plan below
+        // is kept for the right tile column
+        const bool left = gx0 < 0 && c == 0;
+        const gptr gc = src + (left ? 0 : gx0 + (c < 8 ? 16 * c : 120));
+        u32x4 v[NPASS];
+#pragma unroll
+        for (int k = 0; k < NPASS; k++)
+            if (r0 + k * RSTEP < LH)
+                v[k] = *(g_u4*)(gc + (long long)tileplan::mirror1(gy0 + r0 + k * RSTEP, h) * stride);
+#pragma unroll
+        for (int k = 0; k < NPASS; k++) {
+            const int r = r0 + k * RSTEP;
+            if (r >= LH) break;
+            u32x4 t = v[k];
+            if (left)  // columns 0..7 = bytes 8..1, columns 8..15 = bytes 0..7
+                t = u32x4{__builtin_amdgcn_perm(t[2], t[1], 0x01020304u), __builtin_amdgcn_perm(t[1], t[0], 0x01020304u),
+                          t[0], t[1]};
+            uint2* d = reinterpret_cast<uint2*>(&img[r][16 * c]);
+            if (c < 8) {
+                d[0] = make_uint2(t[0], t[1]);
+                d[1] = make_uint2(t[2], t[3]);
+            } else {
+                d[0] = make_uint2(t[2], t[3]);
+            }
+        }
+        return;
+    }
+    {
+        const tileplan::ChunkPlan cp = tileplan::chunk_plan(w, gx0, c);
+        const bool half = tileplan::load_bytes(cp) == 8;
+        u32x4 v[NPASS];
+#pragma unroll
+        for (int k = 0; k < NPASS; k++) {
+            const int r = r0 + k * RSTEP;
+            if (r >= LH) break;
+            const gptr g = src + (long long)tileplan::mirror1(gy0 + r, h) * stride + cp.x;
+            if (half) {
+                const u32x2 t = *(g_u2*)g;
+                v[k][0] = t[0];  // the upper half stays unset (and unread): a write to it would wait
+                v[k][1] = t[1];  // for the loads in flight
+            } else {
+                v[k] = *(g_u4*)g;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < NPASS; k++) {
+            const int r = r0 + k * RSTEP;
+            if (r >= LH) break;
+            const u32x4 t = v[k];
+            u32x4 o;
+            if (cp.kind == tileplan::CHUNK_STRADDLE) {
+                // load byte j = frame column w - 16 + j.  Chunk column pos < n is byte 16 - n + pos
+                // (straddle_direct), column pos >= n is byte 14 + n - pos (straddle_mirror): the
+                // load shifted down by 16 - n bytes, or'ed with the byte reversal of the load
+                // shifted down by n - 1 (both put byte 15 at column n - 1)
+                o = shr_bytes(t, 16 - cp.n) | rev_bytes(shr_bytes(t, cp.n - 1));
+            } else if (cp.kind == tileplan::CHUNK_MIRROR) {
+                o = half ? u32x4{__builtin_bswap32(t[1]), __builtin_bswap32(t[0]), 0u, 0u} : rev_bytes(t);
+            } else if (cp.kind == tileplan::CHUNK_LEFT) {
+                // columns 0..7 = bytes 8..1, columns 8..15 = bytes 0..7
+                o = u32x4{__builtin_amdgcn_perm(t[2], t[1], 0x01020304u), __builtin_amdgcn_perm(t[1], t[0], 0x01020304u),
+                          t[0], t[1]};
+            } else {
+                o = c < 8 ? t : u32x4{t[2], t[3], 0u, 0u};
+            }
+            uint2* d = reinterpret_cast<uint2*>(&img[r][16 * c]);
+            d[0] = make_uint2(o[0], o[1]);
+            if (c < 8) d[1] = make_uint2(o[2], o[3]);
+        }
+    }
+}
+
 // Stage the LW x LH image window into LDS, reflect-101 outside the frame (BORDER_DEFAULT of the
 // reference's GaussianBlur; FAST never reads outside the frame, its range is [3, w-4]).  When
 // the row pitch and the width are multiples of 4, dwords wholly inside the frame are moved with
@@ -248,6 +368,10 @@ __device__ __forceinline__ void load_tile(const uint8_t* __restrict__ src, const
                 }
             }
         }
+        return;
+    }
+    if (p.qword_ok && tileplan::border_ok(p.w, p.h, gx0, gy0)) {
+        load_tile_border(src, p.w, p.h, p.stride, img, gx0, gy0);
         return;
     }
     constexpr int DW = LW / 4;
@@ -543,6 +667,8 @@ __device__ __forceinline__ void blur_mfma(const uint8_t (*img)[LW], const FastPa
     const uint32_t ostep = (uint32_t)p.blur_bcols << 9;
     const bool yok[2] = {n < ylim, 16 + n < ylim};
     for (int s = wave; s < BLUR_STRIPS; s += FAST_THREADS / kWave, off += 128u) {
+        // a strip that starts at or past the blurred frame's stride stores nothing, and neither do
+        // the wave's later ones (right tile column; uniform over the wave)
         // H block b: H rows 16 b - 3 + m (tile coordinates) = LDS rows 16 b + 1 + m; the window
         // is LDS columns 16 s .. + 63 (tile columns 16 s - 8 ..), of which lanes g < 2 load the
         // 32 bytes the band reaches; clamped reads only feed discarded outputs
@@ -3100,6 +3226,44 @@ mage_status mage_orb_fast_gate_stats(mage_orb* orb, uint32_t level, int32_t* las
         MAGE_HIP(hipMemcpyAsync(last_redo, orb->redo.as<uint32_t>() + (size_t)level * (1 + orb->last_batch), 4,
                                 hipMemcpyDeviceToHost, st));
     MAGE_HIP(hipStreamSynchronize(st));
+    return MAGE_OK;
+}
+
+// Host-side view of load_tile's plan for tile (tx, ty) of a w x h frame with `stride` bytes per row
+// (tests/test_fast_tile_plan.py): *path = 0 when the tile takes the generic loop, 1 interior, 2 border.
+// For 1 and 2, loads[(r * 9 + c) * 2 ..] = {byte offset in the frame, bytes} of the load of chunk c of
+// tile row r, and, when img is given, tile[38 * 136] = the tile assembled from img by that plan.
+mage_status mage_debug_fast_tile_plan(const uint8_t* img, int32_t w, int32_t h, int32_t stride, int32_t tx,
+                                      int32_t ty, int32_t* path, int32_t* loads, uint8_t* tile)
+{
+    namespace tp = mage::tileplan;
+    MAGE_REQUIRE(path && loads && w > 0 && h > 0 && stride >= w && tx >= 0 && ty >= 0 && tx * mage::TW < w &&
+                     ty * mage::TH < h && (!img || tile), MAGE_EINVAL, "bad arguments");
+    const int gx0 = tx * mage::TW - 8, gy0 = ty * mage::TH - 4;
+    const bool qword_ok = stride % 8 == 0;
+    const bool interior = gx0 >= 0 && gx0 + mage::LW <= w && gy0 >= 0 && gy0 + mage::LH <= h;
+    *path = !qword_ok ? 0 : interior ? 1 : tp::border_ok(w, h, gx0, gy0) ? 2 : 0;
+    if (*path == 0) return MAGE_OK;
+    for (int r = 0; r < mage::LH; r++)
+        for (int c = 0; c < tp::kChunks; c++) {
+            const tp::ChunkPlan cp = tp::chunk_plan(w, gx0, c);
+            const long long off = (long long)tp::mirror1(gy0 + r, h) * stride + cp.x;
+            const int nb = tp::load_bytes(cp);
+            loads[(r * tp::kChunks + c) * 2] = (int32_t)off;
+            loads[(r * tp::kChunks + c) * 2 + 1] = nb;
+            if (!img) continue;
+            uint8_t* d = tile + r * mage::LW + 16 * c;
+            const uint8_t* b = img + off;
+            if (cp.kind == tp::CHUNK_STRADDLE) {
+                for (int j = 0; j < 16; j++) {
+                    const int pd = tp::straddle_direct(cp.n, j), pm = tp::straddle_mirror(cp.n, j);
+                    if (pd >= 0 && pd < cp.len) d[pd] = b[j];
+                    if (pm >= 0 && pm < cp.len) d[pm] = b[j];
+                }
+            } else {
+                for (int pos = 0; pos < cp.len; pos++) d[pos] = b[tp::chunk_byte(cp, pos)];
+            }
+        }
     return MAGE_OK;
 }
 

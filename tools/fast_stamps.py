@@ -5,7 +5,8 @@
 
 Each wave of the tiles of frames 0..14 stamps s_memtime at the phase boundaries of fast_tile's
 gated path; the table is the mean over waves of each phase's cycles (the wave's own elapsed time,
-which includes the cycles its SIMD spent on other waves) and the share of the wave's lifetime.
+which includes the cycles its SIMD spent on other waves), separately for interior tiles (load_tile's
+interior path) and border tiles.
 """
 import ctypes as C
 import subprocess
@@ -14,8 +15,10 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
 OUT = ROOT / "abl" / "fst"
-NAMES = ["load + barrier", "gate", "listing", "dense barrier", "exact scoring", "scores barrier", "xor tile",
-         "nms + emission", "pre-blur barrier", "blur", "final barrier", "output"]
+# the stamps the gated path writes (slots 9 and 10 belonged to a barrier the kernel no longer has)
+STAMPS = [0, 1, 2, 3, 4, 5, 6, 7, 8, 11, 12]
+NAMES = ["load + barrier", "gate", "listing", "dense barrier", "exact scoring", "(to blur)", "blur",
+         "scores barrier + nms + emission", "final barrier", "output"]
 
 
 def build():
@@ -47,22 +50,37 @@ def run():
     orb.synth_frames_device(frames, B, W, H, 0, synth.FRAME_SEED)
     det = orb.OrbDetector(nfeatures=N)
     st = np.zeros((4096, 2, 16), np.uint64)
-    acc = []
+    # tile of each stamp slot (slot = frame * tiles + T.y * tiles_x + T.x): a tile whose 136 x 38
+    # window lies wholly inside the frame is staged by load_tile's interior path, the rest are
+    # border tiles; the right tile column is listed on its own (its blur strips are partly off-frame)
+    tx_n, ty_n = (W + 119) // 120, (H + 29) // 30
+    slot = np.arange(4096)
+    tx, ty = slot % tx_n, (slot % (tx_n * ty_n)) // tx_n
+    interior = (120 * tx - 8 >= 0) & (120 * tx + 128 <= W) & (30 * ty - 4 >= 0) & (30 * ty + 34 <= H)
+    kind = np.where(interior, 0, np.where(tx == tx_n - 1, 2, 1))
+    kind = np.repeat(kind, 2)  # two waves per tile
+    acc, kinds = [], []
     for it in range(6):
         det.set_fast_gate(89)
         det.detect_and_compute_batch_device(frames, W, H, kp, desc, cnt, N)
         torch.cuda.synchronize()
         L.mage_debug_fast_stamps(st.ctypes.data_as(C.c_void_p))
         if it >= 2:
-            s = st[:, :, :13].reshape(-1, 13).astype(np.int64)
+            s = st[:, :, STAMPS].reshape(-1, len(STAMPS)).astype(np.int64)
             ok = (s[:, 0] > 0) & np.all(np.diff(s, axis=1) >= 0, axis=1)
             acc.append(np.diff(s[ok], axis=1))
+            kinds.append(kind[ok])
     d = np.concatenate(acc)
-    m = d.mean(0)
-    tot = m.sum()
-    print(f"waves {len(d)}, mean lifetime {tot:.0f} cycles")
-    for n, v in zip(NAMES, m):
-        print(f"  {n:18s} {v:8.0f} cycles  {100 * v / tot:5.1f} %")
+    k = np.concatenate(kinds)
+    groups = [("all tiles", k >= 0), ("interior", k == 0), ("border", k != 0),
+              ("border, not right column", k == 1), ("right column", k == 2)]
+    print("mean cycles per wave and phase; gate forced to 89; %dx%d, %d frames" % (W, H, B))
+    print("| phase | " + " | ".join(g for g, _ in groups) + " |")
+    print("|---|" + "---|" * len(groups))
+    print("| waves | " + " | ".join(str(int(m.sum())) for _, m in groups) + " |")
+    for i, n in enumerate(NAMES):
+        print(f"| {n} | " + " | ".join(f"{d[m, i].mean():.0f}" for _, m in groups) + " |")
+    print("| lifetime | " + " | ".join(f"{d[m].sum(1).mean():.0f}" for _, m in groups) + " |")
 
 
 if __name__ == "__main__":
