@@ -288,6 +288,159 @@ inline std::vector<NewMapPoint> CreateInitialAssociations(const NewMapPointsCrea
     return out;
 }
 
+// The association part of NewMapPointsCreationSettings (MageSettings.h:55-61) and Ki's image border.
+struct NewPointsAssociationSettings {
+    float NewMapPointsSearchRadius{11.8816156f};
+    float MaxKeyframeAngleDegrees{60.0f};
+    float KiImageBorder{0.0f};
+    int MaxHammingDistance{30};  // AssociateMatcherSettings
+    int MinHammingDifference{1};
+};
+
+// What LocallyAssociateNewAssociations reads of a covisible keyframe on top of KeyframeView: the
+// descriptors, the unassociated-keypoint mask as IndexedMatch saw it (updated in place: the
+// keypoints CreateInitialAssociations and this call associate become false) and the index the
+// keyframe had among CreateInitialAssociations' covisibleKeyframes (its Kc slot), or -1.
+struct MappingKeyframeView {
+    KeyframeView View;
+    const std::vector<Descriptor>* Descriptors;
+    std::vector<bool>* UnassociatedKeypointMask;
+    int Slot{-1};
+};
+
+struct KeyframeAssociation {
+    int Keyframe;  // index into the covisible keyframes; -1 is Ki
+    uint32_t Keypoint;
+};
+
+// MapPointKeyframeAssociations (NewMapPointsCreation.h): the new point and its Keyframes list,
+// starting {Ki, Kc}.
+struct MapPointKeyframeAssociations {
+    NewMapPoint MapPoint;
+    std::vector<KeyframeAssociation> Keyframes;
+};
+
+inline mage_new_points_settings ToC(const NewMapPointsCreationSettings& settings)
+{
+    mage_new_points_settings s{};
+    s.struct_size = (uint32_t)sizeof(s);
+    s.max_epipolar_error = settings.MaxEpipolarError;
+    s.min_accepted_distance_ratio = settings.MinAcceptedDistanceRatio;
+    s.min_parallax_degrees = settings.MinParallaxDegrees;
+    s.pyramid_scale = settings.PyramidScale;
+    s.num_levels = settings.NumLevels;
+    s.grid_width = settings.NewPointGridWidth;
+    s.grid_height = settings.NewPointGridHeight;
+    s.max_grid_count = settings.NewPointMaxGridCount;
+    s.image_width = settings.ImageWidth;
+    s.image_height = settings.ImageHeight;
+    return s;
+}
+
+// LocallyAssociateNewAssociations (Mapping/NewMapPointsCreation.cpp:337-424): every new point, in
+// order, against every covisible keyframe (in the order CreateInitialAssociations' sort left) it is
+// not yet associated with.  Returns per point the associations gained, in keyframe order; `verdicts`
+// (points x keyframes, MAGE_NA_*) and `records` (projection, octave, keypoint) when given.
+// device < 0 runs the CPU backend.
+inline std::vector<std::vector<KeyframeAssociation>> LocallyAssociateNewAssociations(
+    const NewMapPointsCreationSettings& settings, const NewPointsAssociationSettings& association,
+    const std::vector<Descriptor>& KiDescriptors, const std::vector<MappingKeyframeView>& covisibleKeyframes,
+    const std::vector<NewMapPoint>& newMapPoints, std::vector<uint8_t>* verdicts = nullptr,
+    std::vector<mage_new_point_assoc>* records = nullptr, int device = 0)
+{
+    const mage_new_points_settings s = ToC(settings);
+    mage_new_points_assoc_settings a{};
+    a.struct_size = (uint32_t)sizeof(a);
+    a.search_radius = association.NewMapPointsSearchRadius;
+    a.max_keyframe_angle_degrees = association.MaxKeyframeAngleDegrees;
+    a.image_border = association.KiImageBorder;
+    a.max_hamming_distance = association.MaxHammingDistance;
+    a.min_hamming_difference = association.MinHammingDifference;
+    const uint32_t n_kf = (uint32_t)covisibleKeyframes.size(), n = (uint32_t)newMapPoints.size();
+    std::vector<float> pos, rot, intr;
+    std::vector<KeyPoint> kps;
+    std::vector<uint8_t> desc, mask;
+    std::vector<uint32_t> start(n_kf + 1, 0);
+    std::vector<int32_t> slot(n_kf, -1);
+    for (uint32_t k = 0; k < n_kf; k++) {
+        const MappingKeyframeView& kf = covisibleKeyframes[k];
+        const size_t nk = kf.View.KeyPoints->size();
+        if (kf.Descriptors->size() != nk || kf.UnassociatedKeypointMask->size() != nk)
+            throw std::invalid_argument("a keyframe's keypoints, descriptors and mask must have one length");
+        pos.insert(pos.end(), kf.View.Position.begin(), kf.View.Position.end());
+        rot.insert(rot.end(), kf.View.Rotation.begin(), kf.View.Rotation.end());
+        intr.insert(intr.end(), kf.View.Intrinsics.begin(), kf.View.Intrinsics.end());
+        kps.insert(kps.end(), kf.View.KeyPoints->begin(), kf.View.KeyPoints->end());
+        for (const Descriptor& d : *kf.Descriptors) desc.insert(desc.end(), d.begin(), d.end());
+        mask.insert(mask.end(), kf.UnassociatedKeypointMask->begin(), kf.UnassociatedKeypointMask->end());
+        start[k + 1] = (uint32_t)kps.size();
+        slot[k] = kf.Slot;
+    }
+    std::vector<mage_new_point_assoc> out(std::max<size_t>((size_t)n * n_kf, 1));
+    std::vector<uint8_t> verdict(std::max<size_t>((size_t)n * n_kf, 1), 0xFF);
+    uint32_t status = 0;
+    const uint8_t* kid = KiDescriptors.empty() ? nullptr : KiDescriptors.front().data();
+    if (device < 0)
+        check(mage_new_points_associate_host(&s, &a, newMapPoints.data(), n, kid, (uint32_t)KiDescriptors.size(), n_kf,
+                                             pos.data(), rot.data(), intr.data(), kps.data(), desc.data(), start.data(),
+                                             slot.data(), mask.data(), out.data(), verdict.data(), &status));
+    else
+        check(mage_new_points_associate(&s, &a, newMapPoints.data(), n, kid, (uint32_t)KiDescriptors.size(), n_kf,
+                                        pos.data(), rot.data(), intr.data(), kps.data(), desc.data(), start.data(),
+                                        slot.data(), mask.data(), out.data(), verdict.data(), &status, device));
+    if (status & 1u) throw Error(MAGE_EUNSUPPORTED, "more than 4096 keypoints in a covisible keyframe");
+    std::vector<std::vector<KeyframeAssociation>> gained(n);
+    for (uint32_t p = 0; p < n; p++)
+        for (uint32_t k = 0; k < n_kf; k++)
+            if (verdict[(size_t)p * n_kf + k] == MAGE_NA_ASSOCIATED)
+                gained[p].push_back({(int)k, (uint32_t)out[(size_t)p * n_kf + k].keypoint});
+    for (uint32_t k = 0; k < n_kf; k++)
+        for (uint32_t t = start[k]; t < start[k + 1]; t++)
+            (*covisibleKeyframes[k].UnassociatedKeypointMask)[t - start[k]] = mask[t] != 0;
+    out.resize((size_t)n * n_kf);
+    verdict.resize((size_t)n * n_kf);
+    if (verdicts) *verdicts = verdict;
+    if (records) *records = out;
+    return gained;
+}
+
+// NewMapPointsCreation (Mapping/NewMapPointsCreation.cpp:426-446) after the reference's keyframe
+// bookkeeping: `covisibleKeyframes` are all covisible keyframes in the order of :217, `matches[k]`
+// the IndexedMatch(Kc, Ki) result of keyframe k — empty for a keyframe CreateInitialAssociations
+// skipped or did not reach.  The keyframes with matches are the Kc slots, in order (at most 8).
+// Returns every new point with its Keyframes list {Ki, Kc, gained...}; the keyframes' unassociated
+// masks are updated.  device < 0 runs the CPU backend.
+inline std::vector<MapPointKeyframeAssociations> NewMapPointsCreation(
+    const NewMapPointsCreationSettings& settings, const NewPointsAssociationSettings& association, const KeyframeView& Ki,
+    const std::vector<Descriptor>& KiDescriptors, const std::vector<bool>& KiAssociatedKeypointMask,
+    std::vector<MappingKeyframeView>& covisibleKeyframes, const std::vector<std::vector<DMatch>>& matches, int device = 0)
+{
+    if (matches.size() != covisibleKeyframes.size())
+        throw std::invalid_argument("one match list per covisible keyframe");
+    std::vector<KeyframeView> kc;
+    std::vector<std::vector<DMatch>> kcMatches;
+    std::vector<int> kcOf;
+    for (size_t k = 0; k < covisibleKeyframes.size(); k++) {
+        covisibleKeyframes[k].Slot = -1;
+        if (matches[k].empty()) continue;
+        covisibleKeyframes[k].Slot = (int)kc.size();
+        kc.push_back(covisibleKeyframes[k].View);
+        kcMatches.push_back(matches[k]);
+        kcOf.push_back((int)k);
+    }
+    const std::vector<NewMapPoint> points =
+        CreateInitialAssociations(settings, Ki, KiAssociatedKeypointMask, kc, kcMatches, nullptr, device);
+    const auto gained =
+        LocallyAssociateNewAssociations(settings, association, KiDescriptors, covisibleKeyframes, points, nullptr, nullptr, device);
+    std::vector<MapPointKeyframeAssociations> out(points.size());
+    for (size_t p = 0; p < points.size(); p++) {
+        out[p].MapPoint = points[p];
+        out[p].Keyframes = {{-1, points[p].ki_index}, {kcOf[points[p].kc_slot], points[p].kc_index}};
+        out[p].Keyframes.insert(out[p].Keyframes.end(), gained[p].begin(), gained[p].end());
+    }
+    return out;
+}
+
 struct BundlerParameters {
     bool ArePointsFixed{false};
 };

@@ -469,6 +469,106 @@ mage_status mage_new_map_points_batch_device(const mage_new_points_settings* set
                                              uint32_t cap, uint32_t* d_n_out, uint8_t* d_verdict, uint32_t* d_status,
                                              mage_stream stream);
 
+/* LocallyAssociateNewAssociations (NewMapPointsCreation.cpp:337-424): the second half of
+ * NewMapPointsCreation.  NewMapPointsCreationSettings' association part (MageSettings.h:55-61) and
+ * Ki's image border; mage_new_points_settings supplies pyramid_scale, num_levels and the image
+ * size, which is taken for every keyframe (one camera; the reference reads each keyframe's own
+ * size — stereo pairs with differing sizes are not covered).  struct_size must be
+ * sizeof(mage_new_points_assoc_settings); anything else is MAGE_EINVAL. */
+typedef struct mage_new_points_assoc_settings {
+    uint32_t struct_size;
+    float search_radius;              /* NewMapPointsSearchRadius 11.8816156 (pixels) */
+    float max_keyframe_angle_degrees; /* MaxKeyframeAngleDegrees 60 */
+    float image_border;               /* Ki's GetImageBorder(); the gate uses border - radius / 2 (:345) */
+    int32_t max_hamming_distance;     /* AssociateMatcherSettings.MaxHammingDistance 30, in [-1, 256] */
+    int32_t min_hamming_difference;   /* AssociateMatcherSettings.MinHammingDifference 1 */
+} mage_new_points_assoc_settings;
+
+/* What one new point found in one keyframe: the projection (ProjectUndistorted), the predicted
+ * octave and the keypoint it was associated with, or -1.  A field the reference had not computed
+ * when it skipped or refused the pair is 0 (x, y, octave) or -1 (keypoint): x and y are 0 for
+ * SAME_FRAME and BAD_INDEX (nothing projected), octave is 0 up to and including DISTANCE.
+ * 16 bytes. */
+typedef struct mage_new_point_assoc {
+    float x, y;
+    int32_t octave;
+    int32_t keypoint;
+} mage_new_point_assoc;
+
+/* Verdict of a (point, keyframe) pair: the reference's first reason, in the reference's order. */
+#define MAGE_NA_ASSOCIATED 0 /* Keyframes.push_back + SetKeypointAsAssociated (:408-409) */
+#define MAGE_NA_SAME_FRAME 1 /* the point already has an association with this keyframe (:366-369) */
+#define MAGE_NA_BEHIND 2     /* IsGoodCandidate: depth < 0 (TrackLocalMap.cpp:529) */
+#define MAGE_NA_BORDER 3     /* IsGoodCandidate: outside the image less the border (:529) */
+#define MAGE_NA_ANGLE 4      /* IsGoodCandidate: mean view direction . forward < cos(max angle) (:541) */
+#define MAGE_NA_DISTANCE 5   /* IsGoodCandidate: outside [dMin, dMax] (:549) */
+#define MAGE_NA_OCTAVE 6     /* predicted octave < 0 or > numLevels (:392; the test is >, not >=) */
+#define MAGE_NA_NO_MATCH 7   /* MatchMapPointToCurrentFrame found nothing (:399) */
+#define MAGE_NA_BAD_INDEX 8  /* ki_index >= n_ki, kc_slot >= 8, or kc_index beyond its keyframe: nothing read */
+
+/* The loop of LocallyAssociateNewAssociations over the points mage_new_map_points wrote (outer, in
+ * push_back order) and ALL covisible keyframes (inner, in the order CreateInitialAssociations'
+ * std::sort left, :217): a keyframe the point is already associated with is skipped; the point is
+ * projected (ProjectUndistorted, Tracking/Reprojection.cpp:26-42), gated (TrackLocalMap::
+ * IsGoodCandidate, TrackLocalMap.cpp:519-554, border = image_border - search_radius / 2) and given
+ * an octave (ComputeOctave), then matched by the single-query RadiusMatch (FeatureMatcher.cpp:
+ * 386-446; box, octave, availability and best / second rules as mage_local_map_match) with Ki's
+ * descriptor at the point's ki_index against the keyframe's still-unassociated keypoints; a success
+ * takes the keypoint for every later point.
+ * Keyframe k: pose and calibration as above, keypoints, 32-byte descriptors and mask bytes
+ * concatenated, keyframe k owning [kf_start[k], kf_start[k + 1]).  kf_slot[k] is the Kc slot the
+ * keyframe had in mage_new_map_points, or -1 (in [-1, 7]).  kf_mask is in/out: on entry byte t != 0
+ * means keypoint t was unassociated when IndexedMatch ran; the entry first clears, in keyframe k's
+ * mask, kc_index of every point with kc_slot == kf_slot[k] (CreateInitialAssociations' own
+ * SetKeypointAsAssociated, :314), then runs the loop; on return the taken keypoints are 0 too.
+ * A point with kc_slot == kf_slot[k] is SAME_FRAME for keyframe k (BAD_INDEX when its kc_index is
+ * not a keypoint of k); a point with ki_index >= n_ki or kc_slot >= 8 is BAD_INDEX everywhere.
+ * Outputs are point-major: out[p * n_kf + k], verdict[p * n_kf + k].  *status bit 0: a keyframe has
+ * more than 4096 keypoints — its verdict bytes are left untouched, its records are {0, 0, 0, -1},
+ * its mask is unchanged, the other keyframes are unaffected.  n_points == 0 or n_kf == 0 returns
+ * MAGE_OK with nothing written.  No limit on n_kf.  Host buffers, synchronous, runs on `device`. */
+mage_status mage_new_points_associate(const mage_new_points_settings* settings,
+                                      const mage_new_points_assoc_settings* assoc, const mage_new_point* points,
+                                      uint32_t n_points, const uint8_t* ki_desc, uint32_t n_ki, uint32_t n_kf,
+                                      const float* kf_pos3, const float* kf_r9, const float* kf_intr4,
+                                      const mage_keypoint* kf_kp, const uint8_t* kf_desc, const uint32_t* kf_start,
+                                      const int32_t* kf_slot, uint8_t* kf_mask, mage_new_point_assoc* out,
+                                      uint8_t* verdict, uint32_t* status, int device);
+
+/* The same in plain C++ on the calling thread, with the reference's literal nested loop (points
+ * outer, keyframes inner, the mask updated as it goes): the CPU backend, bit-identical to the
+ * kernel.  No GPU. */
+mage_status mage_new_points_associate_host(const mage_new_points_settings* settings,
+                                           const mage_new_points_assoc_settings* assoc, const mage_new_point* points,
+                                           uint32_t n_points, const uint8_t* ki_desc, uint32_t n_ki, uint32_t n_kf,
+                                           const float* kf_pos3, const float* kf_r9, const float* kf_intr4,
+                                           const mage_keypoint* kf_kp, const uint8_t* kf_desc,
+                                           const uint32_t* kf_start, const int32_t* kf_slot, uint8_t* kf_mask,
+                                           mage_new_point_assoc* out, uint8_t* verdict, uint32_t* status);
+
+/* Batched device form, one workgroup per pair = problem * kf_slots + k.  The points are read as
+ * mage_new_map_points_batch_device leaves them: d_points + problem * cap, count d_n_points[problem]
+ * (a count over cap reads cap).  Ki's descriptors advance by ki_pitch per problem (count
+ * d_n_ki[problem]); keyframe arrays advance per pair (poses 3 / 9 / 4 floats; keypoints,
+ * descriptors and mask bytes kf_pitch entries, count d_n_kf_kp[pair]); problem i uses its first
+ * d_n_kf[i] pairs, d_kf_slot[pair] as kf_slot above.  Records at d_assoc + (problem * cap + p) *
+ * kf_slots + k, verdicts likewise; nothing is written beyond the counts.  The masks are device
+ * bytes, in/out.  Bit 0 of *d_status as above, and also for d_n_kf[problem] > kf_slots (every pair of
+ * that problem is treated as over the limit) or a keypoint count over kf_pitch.  Descriptor
+ * pointers must be 16-byte aligned.  Asynchronous on `stream`: find_leaves, indexed_match_batch,
+ * new_map_points_batch and this entry chain on one stream with no host step. */
+mage_status mage_new_points_associate_batch_device(const mage_new_points_settings* settings,
+                                                   const mage_new_points_assoc_settings* assoc, uint32_t problems,
+                                                   uint32_t kf_slots, const mage_new_point* d_points, uint32_t cap,
+                                                   const uint32_t* d_n_points, const uint8_t* d_ki_desc,
+                                                   int64_t ki_pitch, const uint32_t* d_n_ki, const uint32_t* d_n_kf,
+                                                   const float* d_kf_pos3, const float* d_kf_r9,
+                                                   const float* d_kf_intr4, const mage_keypoint* d_kf_kp,
+                                                   const uint8_t* d_kf_desc, uint8_t* d_kf_mask, int64_t kf_pitch,
+                                                   const uint32_t* d_n_kf_kp, const int32_t* d_kf_slot,
+                                                   mage_new_point_assoc* d_assoc, uint8_t* d_verdict,
+                                                   uint32_t* d_status, mage_stream stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Local bundle adjustment — replaces BundlerLib (Dependencies/BundlerLib/Include/BundlerLib.h) */
 /* ------------------------------------------------------------------------------------------ */

@@ -39,6 +39,7 @@ EXPORTS = [
     "mage_ba_get_stats", "mage_ba_get_state_f64", "mage_ba_pose_batch", "mage_ba_pose_batch_device",
     "mage_track_sequence", "mage_track_sequence_device",
     "mage_new_map_points", "mage_new_map_points_host", "mage_new_map_points_batch_device",
+    "mage_new_points_associate", "mage_new_points_associate_host", "mage_new_points_associate_batch_device",
 ]
 
 
@@ -124,6 +125,16 @@ class NewPointsSettingsC(C.Structure):
         return cls(struct_size=C.sizeof(cls), **kw)
 
 
+class NewPointsAssocSettingsC(C.Structure):
+    """mage_new_points_assoc_settings (include/mage_hot.h); struct_size is filled in by make()."""
+    _fields_ = [("struct_size", C.c_uint32), ("search_radius", C.c_float), ("max_keyframe_angle_degrees", C.c_float),
+                ("image_border", C.c_float), ("max_hamming_distance", C.c_int32), ("min_hamming_difference", C.c_int32)]
+
+    @classmethod
+    def make(cls, **kw):
+        return cls(struct_size=C.sizeof(cls), **kw)
+
+
 class BAStats(C.Structure):
     _fields_ = [("iterations", C.c_uint64), ("trials", C.c_uint64), ("rejected_trials", C.c_uint64),
                 ("last_chi2", C.c_double), ("lambda_", C.c_double)]
@@ -136,6 +147,9 @@ DM_DTYPE = np.dtype([("query_idx", "<i4"), ("train_idx", "<i4"), ("img_idx", "<i
 # mage_new_point (48 B)
 NP_DTYPE = np.dtype([("position", "<f4", 3), ("mean_view_dir", "<f4", 3), ("d_min", "<f4"), ("d_max", "<f4"),
                      ("ki_index", "<u4"), ("kc_slot", "<u4"), ("kc_index", "<u4"), ("match_index", "<u4")])
+
+# mage_new_point_assoc (16 B)
+NA_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("octave", "<i4"), ("keypoint", "<i4")])
 
 _lib = None
 
@@ -259,3 +273,9 @@ def _declare(L: C.CDLL) -> None:
         vp)
     sig("mage_new_map_points_batch_device", st, vp, u32, u32, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp,
         vp, u32, vp, vp, u32, vp, vp, vp, vp)
+    sig("mage_new_points_associate", st, vp, vp, vp, u32, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+        C.c_int)
+    sig("mage_new_points_associate_host", st, vp, vp, vp, u32, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+        vp)
+    sig("mage_new_points_associate_batch_device", st, vp, vp, u32, u32, vp, u32, vp, vp, i64, vp, vp, vp, vp, vp, vp,
+        vp, vp, i64, vp, vp, vp, vp, vp, vp)

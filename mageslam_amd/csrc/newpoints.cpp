@@ -100,3 +100,111 @@ extern "C" mage_status mage_new_map_points_host(const mage_new_points_settings* 
     if (accepted > cap) *status |= 2u;
     return MAGE_OK;
 }
+
+// ------------------------------------------------------------------------------------------
+// LocallyAssociateNewAssociations (NewMapPointsCreation.cpp:337-424): the twin of
+// newpoints_assoc.hip and the CPU backend of mage_new_points_associate.
+// ------------------------------------------------------------------------------------------
+namespace {
+
+int hamming256(const uint8_t* a, const uint8_t* b)
+{
+    int d = 0;
+    for (int i = 0; i < 4; i++) {
+        uint64_t x, y;
+        std::memcpy(&x, a + 8 * i, 8);
+        std::memcpy(&y, b + 8 * i, 8);
+        d += __builtin_popcountll(x ^ y);
+    }
+    return d;
+}
+
+// The single-query RadiusMatch (FeatureMatcher.cpp:386-446) against the available keypoints, the
+// candidates in ascending keypoint index: the keypoint, or -1.
+int radius_match_one(const mage::newpoints::AssocConsts& c, float px, float py, int octave, const uint8_t* desc,
+                     const mage_keypoint* kp, const uint8_t* kdesc, uint32_t n, const uint8_t* mask)
+{
+    const float r = c.radius;
+    int best = c.max_dist + 1, second = 2147483647, train = -1;
+    for (uint32_t t = 0; t < n; t++) {
+        const float tx = kp[t].x, ty = kp[t].y;
+        if (!(tx >= px - r && tx <= px + r && ty >= py - r && ty <= py + r) || kp[t].octave != octave || !mask[t])
+            continue;
+        const int d = hamming256(desc, kdesc + 32ull * t);
+        if (d < best) {
+            train = (int)t;
+            second = best;
+            best = d;
+        }
+    }
+    return train != -1 && second - best > c.min_diff ? train : -1;
+}
+
+}  // namespace
+
+extern "C" mage_status mage_new_points_associate_host(
+    const mage_new_points_settings* settings, const mage_new_points_assoc_settings* assoc, const mage_new_point* points,
+    uint32_t n_points, const uint8_t* ki_desc, uint32_t n_ki, uint32_t n_kf, const float* kf_pos3, const float* kf_r9,
+    const float* kf_intr4, const mage_keypoint* kf_kp, const uint8_t* kf_desc, const uint32_t* kf_start,
+    const int32_t* kf_slot, uint8_t* kf_mask, mage_new_point_assoc* out, uint8_t* verdict, uint32_t* status)
+{
+    using namespace mage;
+    using namespace mage::newpoints;
+    const char* why = check_settings(settings);
+    MAGE_REQUIRE(!why, MAGE_EINVAL, why);
+    why = check_assoc_settings(assoc);
+    MAGE_REQUIRE(!why, MAGE_EINVAL, why);
+    MAGE_REQUIRE(status, MAGE_EINVAL, "null argument");
+    *status = 0;
+    if (n_points == 0 || n_kf == 0) return MAGE_OK;
+    MAGE_REQUIRE(points && out && verdict && kf_pos3 && kf_r9 && kf_intr4 && kf_start && kf_slot && (n_ki == 0 || ki_desc),
+                 MAGE_EINVAL, "null argument");
+    for (uint32_t k = 0; k < n_kf; k++) {
+        MAGE_REQUIRE(kf_start[k] <= kf_start[k + 1], MAGE_EINVAL, "start offsets must not decrease");
+        MAGE_REQUIRE(kf_slot[k] >= -1 && kf_slot[k] < NP_MAX_SLOTS, MAGE_EINVAL, "kf_slot must be in [-1, 7]");
+    }
+    MAGE_REQUIRE(kf_start[n_kf] == kf_start[0] || (kf_kp && kf_desc && kf_mask), MAGE_EINVAL, "null argument");
+    const AssocConsts c = make_assoc_consts(*settings, *assoc);
+    std::vector<Frame> frames(n_kf);
+    for (uint32_t k = 0; k < n_kf; k++) {
+        make_frame(kf_pos3 + 3ull * k, kf_r9 + 9ull * k, kf_intr4 + 4ull * k, frames[k]);
+        const uint32_t nk = kf_start[k + 1] - kf_start[k];
+        if (nk > (uint32_t)NA_MAX_KP) {
+            *status |= 1u;
+            continue;
+        }
+        // CreateInitialAssociations' own associations (:314)
+        for (uint32_t p = 0; p < n_points; p++)
+            if (kf_slot[k] >= 0 && points[p].kc_slot == (uint32_t)kf_slot[k] && points[p].kc_index < nk)
+                kf_mask[kf_start[k] + points[p].kc_index] = 0;
+    }
+    for (uint32_t p = 0; p < n_points; p++) {
+        const mage_new_point& pt = points[p];
+        for (uint32_t k = 0; k < n_kf; k++) {
+            const uint32_t nk = kf_start[k + 1] - kf_start[k];
+            mage_new_point_assoc& o = out[(size_t)p * n_kf + k];
+            o = mage_new_point_assoc{0.f, 0.f, 0, -1};
+            if (nk > (uint32_t)NA_MAX_KP) continue;  // over the limit: the verdict byte stays
+            uint8_t& v = verdict[(size_t)p * n_kf + k];
+            if (pt.ki_index >= n_ki || pt.kc_slot >= (uint32_t)NP_MAX_SLOTS) {
+                v = NA_BAD_INDEX;
+                continue;
+            }
+            if (kf_slot[k] >= 0 && pt.kc_slot == (uint32_t)kf_slot[k]) {
+                v = pt.kc_index < nk ? NA_SAME_FRAME : NA_BAD_INDEX;
+                continue;
+            }
+            v = project_gate(c, frames[k], kf_intr4 + 4ull * k, pt, o.x, o.y, o.octave);
+            if (v != NA_NO_MATCH) continue;
+            uint8_t* mask = kf_mask + kf_start[k];
+            const int t = radius_match_one(c, o.x, o.y, o.octave, ki_desc + 32ull * pt.ki_index, kf_kp + kf_start[k],
+                                           kf_desc + 32ull * kf_start[k], nk, mask);
+            if (t >= 0) {
+                o.keypoint = t;
+                mask[t] = 0;
+                v = NA_ASSOCIATED;
+            }
+        }
+    }
+    return MAGE_OK;
+}

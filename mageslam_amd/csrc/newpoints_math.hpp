@@ -276,5 +276,91 @@ NP_HD int test_cell(const Consts& c, float x, float y)
     return gx + gy * (int)c.grid_w;
 }
 
+// ------------------------------------------------------------------------------------------
+// LocallyAssociateNewAssociations (NewMapPointsCreation.cpp:337-424): what a new point and a
+// covisible keyframe decide before the descriptor search, shared by newpoints_assoc.hip and the
+// twin in newpoints.cpp.
+// ------------------------------------------------------------------------------------------
+constexpr int NA_MAX_KP = 4096;  // keypoints per keyframe (mask bits in LDS)
+
+enum AssocVerdict : uint8_t {
+    NA_ASSOCIATED = 0,
+    NA_SAME_FRAME = 1,
+    NA_BEHIND = 2,
+    NA_BORDER = 3,
+    NA_ANGLE = 4,
+    NA_DISTANCE = 5,
+    NA_OCTAVE = 6,
+    NA_NO_MATCH = 7,
+    NA_BAD_INDEX = 8,
+};
+
+struct AssocConsts {
+    float radius;         // NewMapPointsSearchRadius
+    float border;         // KiImageBorder - NewMapPointsSearchRadius / 2 (:345)
+    float cos_max_angle;  // cosf(deg2rad(MaxKeyframeAngleDegrees))
+    float log2s;          // (float)log2((double)scale)
+    float image_w, image_h;
+    int num_levels;
+    int max_dist, min_diff;
+};
+
+inline const char* check_assoc_settings(const mage_new_points_assoc_settings* a)
+{
+    if (!a) return "null association settings";
+    if (a->struct_size != sizeof(mage_new_points_assoc_settings))
+        return "struct_size is not sizeof(mage_new_points_assoc_settings)";
+    if (!(a->search_radius >= 0.f)) return "search_radius must be >= 0";
+    if (a->max_hamming_distance < -1 || a->max_hamming_distance > 256) return "max_hamming_distance must be in [-1, 256]";
+    return nullptr;
+}
+
+inline AssocConsts make_assoc_consts(const mage_new_points_settings& s, const mage_new_points_assoc_settings& a)
+{
+    AssocConsts c{};
+    c.radius = a.search_radius;
+    c.border = a.image_border - a.search_radius / 2.0f;
+    c.cos_max_angle = cosf(a.max_keyframe_angle_degrees * (3.14159265358979323846f / 180.f));
+    c.log2s = (float)log2((double)s.pyramid_scale);
+    c.image_w = (float)s.image_width;
+    c.image_h = (float)s.image_height;
+    c.num_levels = (int)s.num_levels;
+    c.max_dist = a.max_hamming_distance;
+    c.min_diff = a.min_hamming_difference;
+    return c;
+}
+
+// ProjectUndistorted (Tracking/Reprojection.cpp:26-42), TrackLocalMap::IsGoodCandidate
+// (Tracking/TrackLocalMap.cpp:519-554) and the octave test of :387-395 for one point against one
+// keyframe, in the reference's order.  Returns the first refusal, or NA_NO_MATCH when the point
+// goes on to the descriptor search.  x, y are always set; octave is 0 unless the octave was
+// computed (NA_OCTAVE, NA_NO_MATCH).  A point whose dMin is not positive or whose squared distance
+// is not finite has no octave (the reference's conversion would be undefined): NA_OCTAVE, octave -1.
+NP_HD uint8_t project_gate(const AssocConsts& c, const Frame& f, const float* intr4, const mage_new_point& pt, float& x,
+                           float& y, int& octave)
+{
+    const float* X = pt.position;
+    float cs[3];
+    for (int r = 0; r < 3; r++)
+        cs[r] = (((0.f + f.R[3 * r] * X[0]) + f.R[3 * r + 1] * X[1]) + f.R[3 * r + 2] * X[2]) + f.t[r] * 1.f;
+    const float depth = cs[2], div = depth != 0 ? depth : 1.f;
+    x = (cs[0] / div) * intr4[2] + intr4[0];
+    y = (cs[1] / div) * intr4[3] + intr4[1];
+    octave = 0;
+    if (depth < 0) return NA_BEHIND;
+    if (!(c.border <= x && c.border <= y && x < c.image_w - c.border && y < c.image_h - c.border)) return NA_BORDER;
+    if (dot3(pt.mean_view_dir, &f.R[6]) < c.cos_max_angle) return NA_ANGLE;
+    const float dl[3] = {X[0] - f.C[0], X[1] - f.C[1], X[2] - f.C[2]};
+    const float d2 = (dl[0] * dl[0] + dl[1] * dl[1]) + dl[2] * dl[2];
+    if (d2 < pt.d_min * pt.d_min || pt.d_max * pt.d_max < d2) return NA_DISTANCE;
+    if (!(pt.d_min > 0.f) || !(d2 <= 3.402823466e+38f)) {
+        octave = -1;
+        return NA_OCTAVE;
+    }
+    octave = compute_octave(sqrtf(d2), pt.d_min, c.log2s);
+    if (octave < 0 || octave > c.num_levels) return NA_OCTAVE;
+    return NA_NO_MATCH;
+}
+
 }  // namespace newpoints
 }  // namespace mage
