@@ -29,6 +29,7 @@
 
 #include "common.hpp"
 #include "lds_sort.hpp"
+#include "ordered_take.hpp"
 
 struct mage_bow {
     int device = 0;
@@ -63,14 +64,6 @@ struct IndexedParams {
     uint32_t* status;  // bit 0: a feature set exceeded IM_MAX
 };
 
-__device__ __forceinline__ unsigned hamming32(const uint4& qa, const uint4& qb, const uint8_t* t)
-{
-    const uint4 ta = *reinterpret_cast<const uint4*>(t);
-    const uint4 tb = *reinterpret_cast<const uint4*>(t + 16);
-    return __popc(qa.x ^ ta.x) + __popc(qa.y ^ ta.y) + __popc(qa.z ^ ta.z) + __popc(qa.w ^ ta.w) +
-           __popc(qb.x ^ tb.x) + __popc(qb.y ^ tb.y) + __popc(qb.z ^ tb.z) + __popc(qb.w ^ tb.w);
-}
-
 __global__ __launch_bounds__(256) void bow_leaves_kernel(const uint8_t* __restrict__ nodes,
                                                          const uint32_t* __restrict__ child_start,
                                                          const uint32_t* __restrict__ children,
@@ -89,7 +82,7 @@ __global__ __launch_bounds__(256) void bow_leaves_kernel(const uint8_t* __restri
         uint32_t next = cur;
         for (uint32_t k = c0; k < c1; k++) {
             const uint32_t c = children[k];
-            const unsigned d = hamming32(qa, qb, nodes + 32ull * c);
+            const unsigned d = hamming256(qa, qb, nodes + 32ull * c);
             if (d < best) {
                 best = d;
                 next = c;
@@ -121,7 +114,7 @@ __device__ __forceinline__ void track_run(const unsigned long long* keys, int lo
     unsigned m1 = max_h << 12 | 0xFFFu, m2 = max_h;
     for (int k = lo + sub; k < hi; k += IM_GROUP) {
         const unsigned idx = (unsigned)(keys[k] & 0xFFFFFFFFull);
-        const unsigned d = hamming32(qa, qb, desc + 32ull * idx);
+        const unsigned d = hamming256(qa, qb, desc + 32ull * idx);
         if (d >= max_h) continue;
         const unsigned key = d << 12 | idx;
         if (key < m1) {

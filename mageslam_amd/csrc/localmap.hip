@@ -12,16 +12,10 @@
 //                      within maxHammingDist — only those can ever change the point's result
 //                      (the best starts at maxDist + 1 and only strictly smaller distances count);
 //   lm_resolve_kernel  the points in order: 1024 threads compact the points with candidates into
-//                      LDS, one wave resolves them 64 at a time against the LDS mask — each lane's
-//                      result under the current mask, the keypoints the lanes would take marked
-//                      with the lowest taking lane (LDS atomicMin), and the lanes before the first
-//                      one that sees an earlier lane's keypoint among its candidates are final;
-//                      they commit and the chunk restarts at that lane.  Exactly the sequential
-//                      outcome: a lane's result depends on earlier lanes only through keypoints
-//                      they take from its candidate set.
-// The reference's "second best = the previous best" rule (:425-437) is taken in ascending keypoint
-// order (the R*-tree's visiting order is unspecified), where it is order-free:
-// best = min (distance, index), second = min(maxDist + 1, min distance over lower indices).
+//                      LDS, one wave resolves them 64 at a time against the LDS mask with
+//                      ordered_take.hpp's resolve_in_order, which also says why the speculative
+//                      rounds give exactly the sequential outcome and how the reference's
+//                      "second best" rule is taken.
 // Hiding a pose-estimation outlier's old keypoint from its own point (:192-229) is equivalent to
 // never offering that keypoint to the point: hidden or already taken, it is unavailable either way.
 #include <hip/hip_runtime.h>
@@ -33,6 +27,7 @@
 #include "band_index.hpp"
 #include "common.hpp"
 #include "lds_sort.hpp"
+#include "ordered_take.hpp"
 
 namespace mage {
 namespace {
@@ -40,21 +35,14 @@ namespace {
 constexpr int LM_MAXT = 4096;   // frame keypoints (mask bits in LDS)
 constexpr int LM_CAP = 8;       // candidates kept per point (more: the point rescans its band)
 constexpr int LM_GROUP = 16;    // lanes per point in lm_cand_kernel
+static_assert(LM_MAXT <= OT_MAX_TARGETS, "keypoint indices must fit resolve_in_order's packings");
 
 struct LmRec {
     int n;       // candidates (> LM_CAP: overflow, the entries are not all kept)
     int lo, hi;  // the point's band run in the sorted keys
     int pad;
-    uint32_t e[LM_CAP];  // target << 9 | distance
+    uint32_t e[LM_CAP];  // kept_entry(target, distance)
 };
-
-__device__ __forceinline__ uint32_t hamming32(const uint8_t* a, const uint8_t* b)
-{
-    const uint4 a0 = *reinterpret_cast<const uint4*>(a), a1 = *reinterpret_cast<const uint4*>(a + 16);
-    const uint4 b0 = *reinterpret_cast<const uint4*>(b), b1 = *reinterpret_cast<const uint4*>(b + 16);
-    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-           __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
 
 __global__ __launch_bounds__(SORT_THREADS) void lm_keys_kernel(LocalMapArgs a, unsigned long long* __restrict__ gkeys)
 {
@@ -88,7 +76,7 @@ __device__ __forceinline__ void scan_band(const LocalMapArgs& a, const unsigned 
         const int t = (int)(keys[i] & 0xFFFFFFu);
         const float tx = a.tkp[t].x, ty = a.tkp[t].y;
         if (!(tx >= x0 && tx <= x1 && ty >= y0 && ty <= y1) || t == hide) continue;
-        const uint32_t d = hamming32(qd, a.tdesc + 32ll * t);
+        const uint32_t d = hamming256(qd, a.tdesc + 32ll * t);
         if ((int)d <= a.max_dist) visit(t, (int)d);
     }
 }
@@ -99,7 +87,6 @@ __global__ __launch_bounds__(1024) void lm_cand_kernel(LocalMapArgs a, const uns
     const int nq = (int)*a.nq, nt = (int)*a.nt;
     if (nt > LM_MAXT || nq > (int)a.q_cap) return;
     const int q = (int)((blockIdx.x * 1024 + threadIdx.x) / LM_GROUP), sub = threadIdx.x % LM_GROUP;
-    const int lane = threadIdx.x & 63, gbase = lane & ~(LM_GROUP - 1);
     const bool live = q < nq;
     int lo = 0, hi = 0;
     if (live) {
@@ -108,7 +95,7 @@ __global__ __launch_bounds__(1024) void lm_cand_kernel(LocalMapArgs a, const uns
         lo = lower_bound_keys(keys, nt, band_key(oq, py - r, 0u));
         hi = lower_bound_keys(keys, nt, band_key(oq, py + r, 0xFFFFFFu) + 1ull);
     }
-    // the group walks its run 16 entries at a time; found candidates are compacted with a ballot
+    // the group walks its run 16 entries at a time, appending the found candidates in run order
     int n = 0;
     for (int i0 = lo; __any(live && i0 < hi); i0 += LM_GROUP) {
         bool f = false;
@@ -116,18 +103,14 @@ __global__ __launch_bounds__(1024) void lm_cand_kernel(LocalMapArgs a, const uns
         if (live && i0 + sub < hi) {
             const int i = i0 + sub;
             const int t = (int)(keys[i] & 0xFFFFFFu);
-            const bool avail = (a.mask_words[t >> 5] >> (t & 31)) & 1u;
-            if (avail)
+            if (mask_bit(a.mask_words, t))
                 scan_band(a, keys, q, i, i + 1, 0, 1, [&](int tt, int d) {
                     f = true;
-                    ent = (uint32_t)tt << 9 | (uint32_t)d;
+                    ent = kept_entry(tt, d);
                 });
         }
-        const uint64_t b = __ballot(f);
-        const uint32_t gb = (uint32_t)(b >> gbase) & 0xFFFFu;
-        const int pos = n + __popc(gb & ((1u << sub) - 1u));
+        const int pos = group_append<LM_GROUP>(f, sub, n);
         if (f && pos < LM_CAP) recs[q].e[pos] = ent;
-        n += __popc(gb);
     }
     if (live && sub == 0) {
         recs[q].n = n;
@@ -135,8 +118,6 @@ __global__ __launch_bounds__(1024) void lm_cand_kernel(LocalMapArgs a, const uns
         recs[q].hi = hi;
     }
 }
-
-__device__ __forceinline__ bool bit(const uint32_t* w, int t) { return (w[t >> 5] >> (t & 31)) & 1u; }
 
 __global__ __launch_bounds__(1024) void lm_resolve_kernel(LocalMapArgs a, const unsigned long long* __restrict__ keys,
                                                           const LmRec* __restrict__ recs)
@@ -153,10 +134,11 @@ __global__ __launch_bounds__(1024) void lm_resolve_kernel(LocalMapArgs a, const 
         return;
     }
     for (int i = tid; i < LM_MAXT / 32; i += 1024) m[i] = i < (nt + 31) / 32 ? a.mask_words[i] : 0u;
-    for (int i = tid; i < LM_MAXT; i += 1024) taker[i] = 64;
+    for (int i = tid; i < LM_MAXT; i += 1024) taker[i] = OT_NO_TAKER;
     __syncthreads();
     for (int b0 = 0; b0 < nq; b0 += 1024) {
-        // ordered compaction of this block's points that have candidates
+        // ordered compaction of this block's points that have candidates.  Open-coded: block_prefix's
+        // second barrier (list is not wsum: nothing here needs it) measured +3 % on this kernel.
         const int q = b0 + tid;
         const bool has = q < nq && recs[q].n > 0;
         if (q < nq) a.result[q] = -1;
@@ -170,67 +152,36 @@ __global__ __launch_bounds__(1024) void lm_resolve_kernel(LocalMapArgs a, const 
         }
         if (has) list[off + __popcll(bal & ((1ull << lane) - 1ull))] = q;
         __syncthreads();
-        if (wave == 0) {
-            int c0 = 0;
-            while (c0 < cnt) {
-                const int k = c0 + lane;
-                const bool act = k < cnt;
-                const int qq = act ? list[k] : 0;
-                int n = 0, lo = 0, hi = 0;
-                if (act) {
-                    n = recs[qq].n;
-                    lo = recs[qq].lo;
-                    hi = recs[qq].hi;
-                    for (int e = 0; e < LM_CAP && e < n; e++) ent[lane][e] = recs[qq].e[e];
-                }
-                const bool over = n > LM_CAP;
-                // every available candidate of the lane (overflow: the band rescanned)
-                auto each = [&](auto fn) {
-                    if (!act) return;
-                    if (!over) {
-                        for (int e = 0; e < n; e++) {
-                            const uint32_t v = ent[lane][e];
-                            const int t = (int)(v >> 9);
-                            if (bit(m, t)) fn(t, (int)(v & 0x1FFu));
-                        }
-                    } else {
-                        scan_band(a, keys, qq, lo, hi, 0, 1, [&](int t, int d) {
-                            if (bit(m, t)) fn(t, d);
-                        });
+        if (tid < 64)
+            resolve_in_order(
+                cnt, a.max_dist, a.min_diff, m, taker,
+                [&](int k, bool act) {
+                    const int qq = act ? list[k] : 0;
+                    int n = 0, lo = 0, hi = 0;
+                    if (act) {
+                        n = recs[qq].n;
+                        lo = recs[qq].lo;
+                        hi = recs[qq].hi;
+                        for (int e = 0; e < LM_CAP && e < n; e++) ent[tid][e] = recs[qq].e[e];
                     }
-                };
-                uint32_t bestk = 0xFFFFFFFFu;
-                each([&](int t, int d) { bestk = min(bestk, (uint32_t)d << 12 | (uint32_t)t); });
-                const int tb = (int)(bestk & 0xFFFu), best = (int)(bestk >> 12);
-                int sec = a.max_dist + 1;
-                each([&](int t, int d) {
-                    if (t < tb) sec = min(sec, d);
+                    // every available candidate of the lane (overflow: the band rescanned)
+                    return [=, &a](auto fn) {
+                        if (!act) return;
+                        if (n <= LM_CAP) {
+                            for (int e = 0; e < n; e++) {
+                                const uint32_t v = ent[tid][e];
+                                if (mask_bit(m, kept_target(v))) fn(kept_target(v), kept_dist(v));
+                            }
+                        } else {
+                            scan_band(a, keys, qq, lo, hi, 0, 1, [&](int t, int d) {
+                                if (mask_bit(m, t)) fn(t, d);
+                            });
+                        }
+                    };
+                },
+                [&](int k, bool ok, int t) {
+                    if (ok) a.result[list[k]] = t;
                 });
-                const bool ok = bestk != 0xFFFFFFFFu && sec - best > a.min_diff;
-                if (ok) atomicMin(&taker[tb], lane);
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                bool conflict = false;
-                each([&](int t, int) {
-                    if (taker[t] < lane) conflict = true;
-                });
-                const uint64_t cb = __ballot(conflict);
-                const int f = cb ? __builtin_ctzll(cb) : 64;
-                if (ok && lane < f) {
-                    atomicAnd(&m[tb >> 5], ~(1u << (tb & 31)));
-                    a.result[qq] = tb;
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                if (ok) taker[tb] = 64;
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                c0 += f;
-            }
-        }
         __syncthreads();
     }
     for (int i = tid; i < (nt + 31) / 32; i += 1024) a.mask_words[i] = m[i];

@@ -25,6 +25,7 @@
 
 #include "common.hpp"
 #include "newpoints_math.hpp"
+#include "ordered_take.hpp"
 
 namespace mage {
 namespace {
@@ -149,22 +150,16 @@ __global__ __launch_bounds__(NP_THREADS) void new_points_kernel(NpParams p)
         }
         __syncthreads();
         const bool u = valid && gv == NP_ACCEPTED && s_first[t] == g;
-        int myrank = 0;
-        for (int c = 0; c < ncells; c++) {
-            const unsigned long long bal = __ballot(u && cell == c);
-            if (lane == 0) s_wcell[wave][c] = __popcll(bal);
-            if (cell == c) myrank = __popcll(bal & ((1ull << lane) - 1ull));
-        }
-        __syncthreads();
+        // the match's rank in its cell: the cell's count plus the members of U before it
+        const int r = rank_by_key<NP_WAVES>(cell, u, ncells, s_count, &s_wcell[0][0], NP_MAX_CELLS);
         uint8_t verdict = NP_BAD_INDEX;
-        if (valid) {
-            int r = s_count[cell] + myrank;
-            for (int w = 0; w < wave; w++) r += s_wcell[w][cell];
+        if (valid)
             verdict = (uint32_t)r >= p.c.max_grid_count ? (uint8_t)NP_GRID_FULL
                       : s_first[t] < g                  ? (uint8_t)NP_KI_TAKEN
                                                         : gv;
-        }
         const bool acc = valid && verdict == NP_ACCEPTED;
+        // the accepted points in match order.  Open-coded: block_prefix's second barrier (the next write
+        // of s_wacc is two barriers away already) measured +1 % on this kernel.
         const unsigned long long abal = __ballot(acc);
         if (lane == 0) s_wacc[wave] = __popcll(abal);
         if (live) p.verdict[mi] = verdict;

@@ -15,11 +15,9 @@
 //             touches (box, octave, available under the current mask, distance <= maxDist) into up
 //             to 8 candidates per point — a superset of what the point can ever be offered, since
 //             the mask only loses bits;
-//   resolve   one wave, as localmap.hip's lm_resolve_kernel: each lane's result under the current
-//             mask, the wanted keypoints marked with the lowest wanting lane (LDS atomicMin), the
-//             lanes before the first one that sees an earlier lane's keypoint among its candidates
-//             are final and commit, and the chunk restarts at that lane.  A point with more than 8
-//             candidates rescans its bands instead of reading its list.
+//   resolve   one wave takes the chunk's points in order with ordered_take.hpp's resolve_in_order
+//             (the resolver TrackLocalMap's matching uses; the argument for its exactness is there).
+//             A point with more than 8 candidates rescans its bands instead of reading its list.
 // The first build scanned all of the keyframe's keypoints per point (no index): 0.656 ms per launch
 // on the shape of tools/bench_new_points_assoc.py (256 problems x 8 keyframes x 2000 keypoints), the
 // ~nkp / 4 box tests per lane twice over (72 points are two rounds of 64) being nearly all of it.
@@ -35,6 +33,7 @@
 
 #include "common.hpp"
 #include "newpoints_math.hpp"
+#include "ordered_take.hpp"
 
 namespace mage {
 namespace {
@@ -51,6 +50,7 @@ constexpr int NA_GROUP = 4;   // lanes per point in the gather
 constexpr int NA_CHUNK = 64;  // points per gather + resolve round
 constexpr int NA_BANDS = 32;  // horizontal bands of the keypoint list
 constexpr int NA_BAD_OCT = 15;  // key octave of a keypoint no point can predict (predictions are 0..8)
+static_assert(NA_MAX_KP <= OT_MAX_TARGETS, "keypoint indices must fit resolve_in_order's packings");
 
 struct NaParams {
     AssocConsts c;
@@ -75,15 +75,6 @@ struct NaParams {
     uint32_t* status;
 };
 
-__device__ __forceinline__ uint32_t hamming32(const uint4& a0, const uint4& a1, const uint8_t* b)
-{
-    const uint4 b0 = *reinterpret_cast<const uint4*>(b), b1 = *reinterpret_cast<const uint4*>(b + 16);
-    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-           __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
-
-__device__ __forceinline__ bool bit(const uint32_t* w, int t) { return (w[t >> 5] >> (t & 31)) & 1u; }
-
 // The band of row y: monotone in y (a product with a positive constant, then a clamp), so every
 // keypoint with y0 <= y <= y1 lies in bands band_of(y0) .. band_of(y1).  NaN goes to band 0.
 __device__ __forceinline__ int band_of(float y, float scale)
@@ -92,278 +83,280 @@ __device__ __forceinline__ int band_of(float y, float scale)
     return f >= 0.f ? (f < (float)NA_BANDS ? (int)f : NA_BANDS - 1) : 0;
 }
 
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+// The workgroup's LDS arrays.  The keyframe's Frame is declared beside them in the kernel: on its
+// own the compiler drops the members project_gate never reads (72 bytes).
+struct NaShared {
+    float x[NA_MAX_KP], y[NA_MAX_KP];
+    uint16_t key[NA_MAX_KP];  // by band, ascending keypoint within a band: octave << 12 | keypoint
+    int bstart[NA_BANDS + 1], brun[NA_BANDS];
+    int wband[NA_WAVES][NA_BANDS];
+    uint32_t m[NA_MAX_KP / 32];
+    int taker[NA_MAX_KP];
+    float px[NA_THREADS], py[NA_THREADS];
+    int pi[NA_THREADS];  // the surviving points: index, octave
+    signed char po[NA_THREADS];
+    uint32_t ent[NA_CHUNK][NA_CAP];  // kept_entry(keypoint, distance)
+    int n[NA_CHUNK];
+    uint32_t wsum[NA_WAVES];
+};
 
-__global__ __launch_bounds__(NA_THREADS) void new_points_assoc_kernel(NaParams p)
-{
-    __shared__ float s_x[NA_MAX_KP], s_y[NA_MAX_KP];
-    __shared__ uint16_t s_key[NA_MAX_KP];  // by band, ascending keypoint within a band: octave << 12 | keypoint
-    __shared__ int s_bstart[NA_BANDS + 1], s_brun[NA_BANDS];
-    __shared__ int s_wband[NA_WAVES][NA_BANDS];
-    __shared__ uint32_t s_m[NA_MAX_KP / 32];
-    __shared__ int s_taker[NA_MAX_KP];
-    __shared__ Frame s_frame;
-    __shared__ float s_px[NA_THREADS], s_py[NA_THREADS];
-    __shared__ int s_pi[NA_THREADS];  // the surviving points: index, octave
-    __shared__ signed char s_po[NA_THREADS];
-    __shared__ uint32_t s_ent[NA_CHUNK][NA_CAP];        // keypoint << 9 | distance
-    __shared__ int s_n[NA_CHUNK];
-    __shared__ uint32_t s_wsum[NA_WAVES];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t prob = blockIdx.x / p.kf_slots, k = blockIdx.x % p.kf_slots;
-    const long long pair = blockIdx.x;
-    const uint32_t nkf = p.n_kf[prob], npts = min(p.n_points[prob], p.cap);
-    if (nkf <= p.kf_slots && k >= nkf) return;
-    const uint32_t nkp = p.n_kf_kp[pair];
-    const long long stride = p.kf_slots, o0 = (long long)prob * p.cap * stride + k;
-    mage_new_point_assoc* out = p.out + o0;
-    uint8_t* verdict = p.verdict + o0;
-    if (nkf > p.kf_slots || nkp > (uint32_t)NA_MAX_KP || (long long)nkp > p.kf_pitch) {  // uniform over the workgroup
-        if (tid == 0) atomicOr(p.status, 1u);
-        for (uint32_t i = tid; i < npts; i += NA_THREADS) out[i * stride] = mage_new_point_assoc{0.f, 0.f, 0, -1};
-        return;
-    }
-    const mage_new_point* pts = p.points + (long long)prob * p.cap;
-    const mage_keypoint* kp = p.kf_kp + pair * p.kf_pitch;
-    const uint8_t* kdesc = p.kf_desc + 32ll * pair * p.kf_pitch;
-    uint8_t* mask = p.kf_mask + pair * p.kf_pitch;
-    const uint8_t* kidesc = p.ki_desc + 32ll * prob * p.ki_pitch;
-    const uint32_t nki = (uint32_t)min((long long)p.n_ki[prob], p.ki_pitch);
-    const int slot = p.kf_slot[pair];
-    const float* intr = p.kf_intr4 + 4 * pair;
+// The workgroup's (problem, keyframe) pair.
+struct NaPair {
+    uint32_t nkp, npts, nki;
+    int slot;          // the keyframe's Kc slot, or -1
+    long long stride;  // between a keyframe's records (and verdicts) of consecutive points
+    const mage_new_point* pts;
+    const mage_keypoint* kp;
+    const uint8_t *kdesc, *kidesc;
+    uint8_t* mask;
+    const float* intr;
+    mage_new_point_assoc* out;
+    uint8_t* verdict;
+};
 
-    // the keyframe in LDS, and the band populations
-    if (tid < NA_BANDS) s_bstart[tid + 1] = 0;
-    if (tid == 0) s_bstart[0] = 0;
+// The keyframe in LDS and its keypoints listed by band.
+__device__ __forceinline__ void stage_keyframe(const NaParams& p, const NaPair& v, NaShared& s, Frame& frame,
+                                               long long pair)
+{
+    const int tid = threadIdx.x, lane = tid & 63;
+    if (tid < NA_BANDS) s.bstart[tid + 1] = 0;
+    if (tid == 0) s.bstart[0] = 0;
     __syncthreads();
-    for (int i = tid; i < (int)nkp; i += NA_THREADS) {
-        const float y = kp[i].y;
-        s_x[i] = kp[i].x;
-        s_y[i] = y;
-        atomicAdd(&s_bstart[band_of(y, p.band_scale) + 1], 1);
+    for (int i = tid; i < (int)v.nkp; i += NA_THREADS) {
+        const float y = v.kp[i].y;
+        s.x[i] = v.kp[i].x;
+        s.y[i] = y;
+        atomicAdd(&s.bstart[band_of(y, p.band_scale) + 1], 1);
     }
-    for (int i = tid; i < NA_MAX_KP; i += NA_THREADS) s_taker[i] = 64;
+    for (int i = tid; i < NA_MAX_KP; i += NA_THREADS) s.taker[i] = OT_NO_TAKER;
     for (int c0 = 0; c0 < NA_MAX_KP; c0 += NA_THREADS) {  // a wave's 64 mask bytes are two words (all 128 are written)
         const int t = c0 + tid;
-        const unsigned long long bal = __ballot(t < (int)nkp && mask[t] != 0);
+        const unsigned long long bal = __ballot(t < (int)v.nkp && v.mask[t] != 0);
         if (lane == 0) {
-            s_m[t >> 5] = (uint32_t)bal;
-            s_m[(t >> 5) + 1] = (uint32_t)(bal >> 32);
+            s.m[t >> 5] = (uint32_t)bal;
+            s.m[(t >> 5) + 1] = (uint32_t)(bal >> 32);
         }
     }
     if (tid == 0) {
         Frame f;
-        make_frame(p.kf_pos3 + 3 * pair, p.kf_r9 + 9 * pair, intr, f);
-        s_frame = f;
+        make_frame(p.kf_pos3 + 3 * pair, p.kf_r9 + 9 * pair, v.intr, f);
+        frame = f;
     }
     __syncthreads();
     if (tid == 0) {
         int acc = 0;
         for (int b = 0; b < NA_BANDS; b++) {
-            s_brun[b] = acc;
-            acc += s_bstart[b + 1];
-            s_bstart[b + 1] = acc;
+            s.brun[b] = acc;
+            acc += s.bstart[b + 1];
+            s.bstart[b + 1] = acc;
         }
     }
     __syncthreads();
-    // the list: 256 keypoints at a time, each one's rank among its band's keypoints of the chunk by
-    // wave ballots plus the band's running base
-    for (int c0 = 0; c0 < (int)nkp; c0 += NA_THREADS) {
+    // the list: 256 keypoints at a time, each at its band's running base plus its rank among the
+    // band's keypoints of the chunk
+    for (int c0 = 0; c0 < (int)v.nkp; c0 += NA_THREADS) {
         const int t = c0 + tid;
-        const int b = t < (int)nkp ? band_of(s_y[t], p.band_scale) : -1;
-        const int o = b >= 0 ? kp[t].octave : 0;  // in flight over the ballots
-        int rank = 0;
-        for (int c = 0; c < NA_BANDS; c++) {
-            const unsigned long long bal = __ballot(b == c);
-            if (lane == 0) s_wband[wave][c] = __popcll(bal);
-            if (b == c) rank = __popcll(bal & ((1ull << lane) - 1ull));
-        }
-        __syncthreads();
+        const int b = t < (int)v.nkp ? band_of(s.y[t], p.band_scale) : -1;
+        const int o = b >= 0 ? v.kp[t].octave : 0;  // in flight over the ballots
+        const int pos = rank_by_key<NA_WAVES>(b, true, NA_BANDS, s.brun, &s.wband[0][0], NA_BANDS);
         int add = 0;
         if (tid < NA_BANDS)
-            for (int w = 0; w < NA_WAVES; w++) add += s_wband[w][tid];
-        if (b >= 0) {
-            int pos = s_brun[b] + rank;
-            for (int w = 0; w < wave; w++) pos += s_wband[w][b];
-            s_key[pos] = (uint16_t)((o >= 0 && o < NA_BAD_OCT ? o : NA_BAD_OCT) << 12 | t);
-        }
-        __syncthreads();  // s_wband and s_brun are read: the next chunk may write them
-        if (tid < NA_BANDS) s_brun[tid] += add;  // read again only after the next chunk's first barrier
+            for (int w = 0; w < NA_WAVES; w++) add += s.wband[w][tid];
+        if (b >= 0) s.key[pos] = (uint16_t)((o >= 0 && o < NA_BAD_OCT ? o : NA_BAD_OCT) << 12 | t);
+        __syncthreads();  // wband and brun are read: the next chunk may write them
+        if (tid < NA_BANDS) s.brun[tid] += add;  // read again only after the next chunk's first barrier
     }
     __syncthreads();
-    // CreateInitialAssociations' own associations with this keyframe (:314)
-    if (slot >= 0)
-        for (uint32_t i = tid; i < npts; i += NA_THREADS) {
-            const uint32_t s = pts[i].kc_slot, q = pts[i].kc_index;
-            if (s == (uint32_t)slot && q < nkp) atomicAnd(&s_m[q >> 5], ~(1u << (q & 31)));
+}
+
+// CreateInitialAssociations' own associations with this keyframe (:314) leave the mask.
+__device__ __forceinline__ void clear_claims(const NaPair& v, NaShared& s)
+{
+    if (v.slot >= 0)
+        for (uint32_t i = threadIdx.x; i < v.npts; i += NA_THREADS) {
+            const uint32_t sl = v.pts[i].kc_slot, q = v.pts[i].kc_index;
+            if (sl == (uint32_t)v.slot && q < v.nkp) mask_clear(s.m, (int)q);
         }
     __syncthreads();
+}
 
-    const float r = p.c.radius;
-    const int maxd = p.c.max_dist, mind = p.c.min_diff;
-    for (uint32_t c0 = 0; c0 < npts; c0 += NA_THREADS) {
-        // gate: one thread per point
-        const uint32_t i = c0 + tid;
-        bool pass = false;
-        float px = 0.f, py = 0.f;
-        int oc = 0;
-        if (i < npts) {
-            const mage_new_point pt = pts[i];
-            uint8_t v;
-            if (pt.ki_index >= nki || pt.kc_slot >= (uint32_t)NP_MAX_SLOTS)
-                v = NA_BAD_INDEX;
-            else if (slot >= 0 && pt.kc_slot == (uint32_t)slot)
-                v = pt.kc_index < nkp ? NA_SAME_FRAME : NA_BAD_INDEX;
-            else {
-                v = project_gate(p.c, s_frame, intr, pt, px, py, oc);
-                pass = v == NA_NO_MATCH;
-            }
-            if (!pass) {
-                out[i * stride] = mage_new_point_assoc{px, py, oc, -1};
-                verdict[i * stride] = v;
-            }
+// Points c0 .. c0 + 255, one thread each: a refused point's record and verdict are final, the others
+// are compacted in point order into px, py, pi, po.  Returns their count.
+__device__ __forceinline__ int gate_and_compact(const NaParams& p, const NaPair& v, NaShared& s, const Frame& frame,
+                                                uint32_t c0)
+{
+    const uint32_t i = c0 + threadIdx.x;
+    bool pass = false;
+    float px = 0.f, py = 0.f;
+    int oc = 0;
+    if (i < v.npts) {
+        const mage_new_point pt = v.pts[i];
+        uint8_t vd;
+        if (pt.ki_index >= v.nki || pt.kc_slot >= (uint32_t)NP_MAX_SLOTS)
+            vd = NA_BAD_INDEX;
+        else if (v.slot >= 0 && pt.kc_slot == (uint32_t)v.slot)
+            vd = pt.kc_index < v.nkp ? NA_SAME_FRAME : NA_BAD_INDEX;
+        else {
+            vd = project_gate(p.c, frame, v.intr, pt, px, py, oc);
+            pass = vd == NA_NO_MATCH;
         }
-        const unsigned long long bal = __ballot(pass);
-        if (lane == 0) s_wsum[wave] = (uint32_t)__popcll(bal);
-        __syncthreads();
-        int off = 0, cnt = 0;
-        for (int w = 0; w < NA_WAVES; w++) {
-            off += w < wave ? (int)s_wsum[w] : 0;
-            cnt += (int)s_wsum[w];
+        if (!pass) {
+            v.out[i * v.stride] = mage_new_point_assoc{px, py, oc, -1};
+            v.verdict[i * v.stride] = vd;
         }
-        if (pass) {
-            const int pos = off + __popcll(bal & ((1ull << lane) - 1ull));
-            s_px[pos] = px;
-            s_py[pos] = py;
-            s_pi[pos] = (int)i;
-            s_po[pos] = (signed char)oc;
-        }
-        __syncthreads();
+    }
+    uint32_t cnt;
+    const uint32_t pos = block_prefix<NA_WAVES>(pass, s.wsum, &cnt);
+    if (pass) {
+        s.px[pos] = px;
+        s.py[pos] = py;
+        s.pi[pos] = (int)i;
+        s.po[pos] = (signed char)oc;
+    }
+    __syncthreads();
+    return (int)cnt;
+}
 
+// A surviving point's search: its box, its octave, its run of the band list, its descriptor.
+struct Box {
+    float x0, x1, y0, y1;
+    int qo, lo, hi;
+    uint4 a0, a1;
+};
+
+__device__ __forceinline__ Box load_box(const NaParams& p, const NaPair& v, const NaShared& s, int i)
+{
+    const float r = p.c.radius, qx = s.px[i], qy = s.py[i];
+    Box b;
+    b.x0 = qx - r, b.x1 = qx + r, b.y0 = qy - r, b.y1 = qy + r;
+    b.qo = s.po[i];
+    b.lo = s.bstart[band_of(b.y0, p.band_scale)];
+    b.hi = s.bstart[band_of(b.y1, p.band_scale) + 1];
+    const uint8_t* qd = v.kidesc + 32ll * v.pts[s.pi[i]].ki_index;
+    b.a0 = *reinterpret_cast<const uint4*>(qd);
+    b.a1 = *reinterpret_cast<const uint4*>(qd + 16);
+    return b;
+}
+
+// Entries lo + first, lo + first + step, ... of the box's run: `visit(t, d)` for every keypoint in
+// the box with the box's octave that is available under the current mask and within maxDist.
+template <typename F>
+__device__ __forceinline__ void scan(const NaParams& p, const NaPair& v, const NaShared& s, const Box& b, int first,
+                                     int step, F visit)
+{
+    for (int i = b.lo + first; i < b.hi; i += step) {
+        const int key = s.key[i], t = key & 0xFFF;
+        const float tx = s.x[t], ty = s.y[t];
+        if (!(tx >= b.x0 && tx <= b.x1 && ty >= b.y0 && ty <= b.y1) || (key >> 12) != b.qo || !mask_bit(s.m, t)) continue;
+        const int d = (int)hamming256(b.a0, b.a1, v.kdesc + 32ll * t);
+        if (d <= p.c.max_dist) visit(t, d);
+    }
+}
+
+// Surviving points s0 .. s0 + 63, 4 lanes per point walking the point's run 4 entries at a time: up
+// to 8 candidates per point into ent, their number into n.
+__device__ __forceinline__ void gather(const NaParams& p, const NaPair& v, NaShared& s, int s0, int cnt)
+{
+    const int j = threadIdx.x / NA_GROUP, sub = threadIdx.x % NA_GROUP;
+    const bool act = s0 + j < cnt;
+    Box b = {};
+    if (act) b = load_box(p, v, s, s0 + j);
+    int n = 0;
+    for (int i0 = b.lo; __any(i0 < b.hi); i0 += NA_GROUP) {
+        bool f = false;
+        uint32_t ent = 0;
+        if (i0 + sub < b.hi) {
+            Box one = b;  // this lane's entry alone
+            one.lo = i0 + sub;
+            one.hi = one.lo + 1;
+            scan(p, v, s, one, 0, 1, [&](int t, int d) {
+                f = true;
+                ent = kept_entry(t, d);
+            });
+        }
+        const int pos = group_append<NA_GROUP>(f, sub, n);
+        if (f && pos < NA_CAP) s.ent[j][pos] = ent;
+    }
+    if (act && sub == 0) s.n[j] = n;
+}
+
+// One wave: the chunk's cc points take their keypoints in order; every point's record and verdict.
+__device__ __forceinline__ void resolve(const NaParams& p, const NaPair& v, NaShared& s, int s0, int cc)
+{
+    resolve_in_order(
+        cc, p.c.max_dist, p.c.min_diff, s.m, s.taker,
+        [&](int j, bool act) {
+            const int n = act ? s.n[j] : 0;
+            Box b = {};
+            if (n > NA_CAP) b = load_box(p, v, s, s0 + j);
+            // every candidate of the lane that is still available (overflow: the bands rescanned)
+            return [=, &p, &v, &s](auto fn) {
+                if (n <= NA_CAP) {
+                    for (int e = 0; e < n; e++) {
+                        const uint32_t c = s.ent[j][e];
+                        if (mask_bit(s.m, kept_target(c))) fn(kept_target(c), kept_dist(c));
+                    }
+                } else {
+                    scan(p, v, s, b, 0, 1, fn);
+                }
+            };
+        },
+        [&](int j, bool ok, int t) {
+            const int i = s0 + j;
+            const long long o = (long long)s.pi[i] * v.stride;
+            v.out[o] = mage_new_point_assoc{s.px[i], s.py[i], s.po[i], ok ? t : -1};
+            v.verdict[o] = ok ? (uint8_t)NA_ASSOCIATED : (uint8_t)NA_NO_MATCH;
+        });
+}
+
+// The taken keypoints (the claims included) back to the mask bytes.
+__device__ __forceinline__ void write_mask(const NaPair& v, const NaShared& s)
+{
+    for (int t = threadIdx.x; t < (int)v.nkp; t += NA_THREADS)
+        if (!mask_bit(s.m, t)) v.mask[t] = 0;
+}
+
+__global__ __launch_bounds__(NA_THREADS) void new_points_assoc_kernel(NaParams p)
+{
+    __shared__ NaShared s;
+    __shared__ Frame s_frame;
+    const int tid = threadIdx.x;
+    const uint32_t prob = blockIdx.x / p.kf_slots, k = blockIdx.x % p.kf_slots;
+    const long long pair = blockIdx.x;
+    const uint32_t nkf = p.n_kf[prob];
+    if (nkf <= p.kf_slots && k >= nkf) return;
+    NaPair v;
+    v.nkp = p.n_kf_kp[pair];
+    v.npts = min(p.n_points[prob], p.cap);
+    v.stride = p.kf_slots;
+    v.out = p.out + (long long)prob * p.cap * v.stride + k;
+    v.verdict = p.verdict + (long long)prob * p.cap * v.stride + k;
+    if (nkf > p.kf_slots || v.nkp > (uint32_t)NA_MAX_KP || (long long)v.nkp > p.kf_pitch) {  // uniform over the workgroup
+        if (tid == 0) atomicOr(p.status, 1u);
+        for (uint32_t i = tid; i < v.npts; i += NA_THREADS) v.out[i * v.stride] = mage_new_point_assoc{0.f, 0.f, 0, -1};
+        return;
+    }
+    v.pts = p.points + (long long)prob * p.cap;
+    v.kp = p.kf_kp + pair * p.kf_pitch;
+    v.kdesc = p.kf_desc + 32ll * pair * p.kf_pitch;
+    v.mask = p.kf_mask + pair * p.kf_pitch;
+    v.kidesc = p.ki_desc + 32ll * prob * p.ki_pitch;
+    v.nki = (uint32_t)min((long long)p.n_ki[prob], p.ki_pitch);
+    v.slot = p.kf_slot[pair];
+    v.intr = p.kf_intr4 + 4 * pair;
+
+    stage_keyframe(p, v, s, s_frame, pair);
+    clear_claims(v, s);
+    for (uint32_t c0 = 0; c0 < v.npts; c0 += NA_THREADS) {
+        const int cnt = gate_and_compact(p, v, s, s_frame, c0);
         for (int s0 = 0; s0 < cnt; s0 += NA_CHUNK) {
-            // gather: 4 lanes per point walk the point's bands 4 keypoints at a time
-            {
-                const int j = tid / NA_GROUP, sub = tid % NA_GROUP, gbase = lane & ~(NA_GROUP - 1);
-                const bool act = s0 + j < cnt;
-                float x0 = 0.f, x1 = 0.f, y0 = 0.f, y1 = 0.f;
-                int qo = -2, lo = 0, hi = 0;
-                uint4 a0 = make_uint4(0, 0, 0, 0), a1 = a0;
-                if (act) {
-                    const float qx = s_px[s0 + j], qy = s_py[s0 + j];
-                    x0 = qx - r, x1 = qx + r, y0 = qy - r, y1 = qy + r;
-                    qo = s_po[s0 + j];
-                    lo = s_bstart[band_of(y0, p.band_scale)];
-                    hi = s_bstart[band_of(y1, p.band_scale) + 1];
-                    const uint8_t* qd = kidesc + 32ll * pts[s_pi[s0 + j]].ki_index;
-                    a0 = *reinterpret_cast<const uint4*>(qd);
-                    a1 = *reinterpret_cast<const uint4*>(qd + 16);
-                }
-                int n = 0;
-                for (int i0 = lo; __any(i0 < hi); i0 += NA_GROUP) {
-                    const int e = i0 + sub;
-                    bool f = false;
-                    uint32_t ent = 0;
-                    if (e < hi) {
-                        const int key = s_key[e], t = key & 0xFFF;
-                        const float tx = s_x[t], ty = s_y[t];
-                        if (tx >= x0 && tx <= x1 && ty >= y0 && ty <= y1 && (key >> 12) == qo && bit(s_m, t)) {
-                            const uint32_t d = hamming32(a0, a1, kdesc + 32ll * t);
-                            if ((int)d <= maxd) {
-                                f = true;
-                                ent = (uint32_t)t << 9 | d;
-                            }
-                        }
-                    }
-                    const unsigned long long b = __ballot(f);
-                    const uint32_t gb = (uint32_t)(b >> gbase) & ((1u << NA_GROUP) - 1u);
-                    const int pos = n + __popc(gb & ((1u << sub) - 1u));
-                    if (f && pos < NA_CAP) s_ent[j][pos] = ent;
-                    n += __popc(gb);
-                }
-                if (act && sub == 0) s_n[j] = n;
-            }
+            gather(p, v, s, s0, cnt);
             __syncthreads();
-            // resolve: one wave, the chunk's points in order
-            if (wave == 0) {
-                const int cc = min(NA_CHUNK, cnt - s0);
-                int r0 = 0;
-                while (r0 < cc) {
-                    const int j = r0 + lane;
-                    const bool act = j < cc;
-                    const int n = act ? s_n[j] : 0;
-                    const bool over = n > NA_CAP;
-                    float x0 = 0.f, x1 = 0.f, y0 = 0.f, y1 = 0.f;
-                    int qo = -2, lo = 0, hi = 0;
-                    uint4 a0 = make_uint4(0, 0, 0, 0), a1 = a0;
-                    if (over) {
-                        const float qx = s_px[s0 + j], qy = s_py[s0 + j];
-                        x0 = qx - r, x1 = qx + r, y0 = qy - r, y1 = qy + r;
-                        qo = s_po[s0 + j];
-                        lo = s_bstart[band_of(y0, p.band_scale)];
-                        hi = s_bstart[band_of(y1, p.band_scale) + 1];
-                        const uint8_t* qd = kidesc + 32ll * pts[s_pi[s0 + j]].ki_index;
-                        a0 = *reinterpret_cast<const uint4*>(qd);
-                        a1 = *reinterpret_cast<const uint4*>(qd + 16);
-                    }
-                    // every candidate of the lane that is still available (overflow: the bands rescanned)
-                    auto each = [&](auto fn) {
-                        if (!act) return;
-                        if (!over) {
-                            for (int e = 0; e < n; e++) {
-                                const uint32_t v = s_ent[j][e];
-                                const int t = (int)(v >> 9);
-                                if (bit(s_m, t)) fn(t, (int)(v & 0x1FFu));
-                            }
-                        } else {
-                            for (int i = lo; i < hi; i++) {
-                                const int key = s_key[i], t = key & 0xFFF;
-                                const float tx = s_x[t], ty = s_y[t];
-                                if (!(tx >= x0 && tx <= x1 && ty >= y0 && ty <= y1) || (key >> 12) != qo || !bit(s_m, t))
-                                    continue;
-                                const int d = (int)hamming32(a0, a1, kdesc + 32ll * t);
-                                if (d <= maxd) fn(t, d);
-                            }
-                        }
-                    };
-                    uint32_t bestk = 0xFFFFFFFFu;
-                    each([&](int t, int d) { bestk = min(bestk, (uint32_t)d << 12 | (uint32_t)t); });
-                    const int tb = (int)(bestk & 0xFFFu), best = (int)(bestk >> 12);
-                    int sec = maxd + 1;
-                    each([&](int t, int d) {
-                        if (t < tb) sec = min(sec, d);
-                    });
-                    const bool ok = bestk != 0xFFFFFFFFu && sec - best > mind;
-                    if (ok) atomicMin(&s_taker[tb], lane);
-                    wave_sync();
-                    bool conflict = false;
-                    each([&](int t, int) {
-                        if (s_taker[t] < lane) conflict = true;
-                    });
-                    const unsigned long long cb = __ballot(conflict);
-                    const int f = cb ? __builtin_ctzll(cb) : 64;
-                    if (act && lane < f) {
-                        if (ok) atomicAnd(&s_m[tb >> 5], ~(1u << (tb & 31)));
-                        const long long o = (long long)s_pi[s0 + j] * stride;
-                        out[o] = mage_new_point_assoc{s_px[s0 + j], s_py[s0 + j], s_po[s0 + j], ok ? tb : -1};
-                        verdict[o] = ok ? (uint8_t)NA_ASSOCIATED : (uint8_t)NA_NO_MATCH;
-                    }
-                    wave_sync();
-                    if (ok) s_taker[tb] = 64;
-                    wave_sync();
-                    r0 += f;
-                }
-            }
+            if (tid < kWave) resolve(p, v, s, s0, min(NA_CHUNK, cnt - s0));
             __syncthreads();
         }
     }
-    // the taken keypoints (the claims included) back to the mask bytes
-    for (int t = tid; t < (int)nkp; t += NA_THREADS)
-        if (!bit(s_m, t)) mask[t] = 0;
+    write_mask(v, s);
 }
 
 }  // namespace

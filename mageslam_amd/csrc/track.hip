@@ -26,6 +26,7 @@
 
 #include "common.hpp"
 #include "depth_noise.hpp"
+#include "ordered_take.hpp"
 
 namespace mage {
 namespace {
@@ -80,25 +81,6 @@ __device__ void store_pose(double* p, const DPose& q)
 {
     for (int i = 0; i < 9; i++) p[i] = q.R[i];
     for (int i = 0; i < 3; i++) p[9 + i] = q.t[i];
-}
-
-// Exclusive position of this thread's item among the block's items with pr set, in thread order;
-// *total = their count.  wsum: 16 words of LDS.
-__device__ uint32_t block_prefix(bool pr, uint32_t* wsum, uint32_t* total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t b = __ballot(pr);
-    const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-    if (lane == 0) wsum[wave] = (uint32_t)__builtin_popcountll(b);
-    __syncthreads();
-    uint32_t woff = 0, tot = 0;
-    for (int w = 0; w < TT / 64; w++) {
-        if (w < wave) woff += wsum[w];
-        tot += wsum[w];
-    }
-    __syncthreads();
-    *total = tot;
-    return woff + before;
 }
 
 constexpr int NKMAX = 8;  // keyframes of the local map
@@ -338,7 +320,7 @@ __device__ void project_frame(const TrackBufs& b, const TrackConst& c, int f, co
             v = (xc[1] / xc[2]) * c.fy + c.cy;
         }
         uint32_t tot;
-        const uint32_t pos = base + block_prefix(front, wsum, &tot);
+        const uint32_t pos = base + block_prefix<TT / 64>(front, wsum, &tot);
         if (front) {
             b.qkp[pos] = b.kf_kp[o + i];
             const uint4* s = reinterpret_cast<const uint4*>(b.kf_desc + 32ull * (o + i));
@@ -422,7 +404,7 @@ __device__ void filter_frame(const TrackBufs& b, const TrackConst& c, const uint
         const uint32_t k = c0 + threadIdx.x;
         const bool keep = k < n && !b.out1[k];
         uint32_t tot;
-        const uint32_t pos = base + block_prefix(keep, wsum, &tot);
+        const uint32_t pos = base + block_prefix<TT / 64>(keep, wsum, &tot);
         if (keep) {
             for (int j = 0; j < 3; j++) b.pts2[3 * pos + j] = b.pts1[3 * k + j];
             b.uv2[2 * pos] = b.uv1[2 * k];
@@ -522,7 +504,7 @@ __device__ void lm_project_frame(const TrackBufs& b, const TrackConst& c)
                 }
             }
             uint32_t tot;
-            const uint32_t pos = base + block_prefix(ok, wsum, &tot);
+            const uint32_t pos = base + block_prefix<TT / 64>(ok, wsum, &tot);
             if (ok && pos < c.qcap) {
                 b.lm_qpos[2 * pos] = px;
                 b.lm_qpos[2 * pos + 1] = py;
@@ -554,7 +536,7 @@ __global__ __launch_bounds__(TT) void trk_lm_assemble(TrackBufs b, const mage_ke
         const uint32_t q = c0 + threadIdx.x;
         const int r = q < nq ? b.lm_res[q] : -1;
         uint32_t tot;
-        const uint32_t pos = base + block_prefix(r >= 0, wsum, &tot);
+        const uint32_t pos = base + block_prefix<TT / 64>(r >= 0, wsum, &tot);
         if (r >= 0) {
             for (int j = 0; j < 3; j++) b.pts2[3 * pos + j] = b.lm_qpt[3 * q + j];
             b.uv2[2 * pos] = fk[r].x;
@@ -583,7 +565,7 @@ __device__ void finish_frame(const TrackBufs& b, const TrackConst& c, int f, con
         for (uint32_t c0 = 0; c0 < n2; c0 += TT) {
             const uint32_t k = c0 + threadIdx.x;
             uint32_t tot;
-            (void)block_prefix(k < n2 && !b.out2[k], wsum, &tot);
+            (void)block_prefix<TT / 64>(k < n2 && !b.out2[k], wsum, &tot);
             n_in += tot;
         }
         // TrackLocalMap.cpp:309-314: too few associations after the second pass
@@ -627,7 +609,7 @@ __device__ void finish_frame(const TrackBufs& b, const TrackConst& c, int f, con
             const uint32_t k = c0 + threadIdx.x;
             const bool in = k < n2 && !b.out2[k];
             uint32_t tot;
-            const uint32_t pos = base + block_prefix(in, wsum, &tot);
+            const uint32_t pos = base + block_prefix<TT / 64>(in, wsum, &tot);
             if (in && pos < c.acap) {
                 as[pos] = make_int4(b.src2[k].x, b.src2[k].y, __float_as_int(b.uv2[2 * k]), __float_as_int(b.uv2[2 * k + 1]));
                 aa[pos] = 1;

@@ -271,10 +271,11 @@ def _count(n, name, seed):
     return sc.case(name)
 
 
-def _blob():
-    """100 points projecting into one search box of a keyframe that has 40 near-identical keypoints
-    there: more candidates than any per-point capacity, and chains of conflicts (min_hamming_difference 0, so
-    that a point with any candidate takes one)."""
+def _blob(size, name):
+    """100 points projecting into one search box of a keyframe that has `size` near-identical keypoints
+    there, and chains of conflicts (min_hamming_difference 0, so that a point with any candidate takes
+    one).  40: more candidates than any per-point capacity; 8 and 9: the kernel's kept list of 8
+    exactly full, and its first overflow."""
     sc = Scene(49, 100, n_slots=1, octaves=(1,), window=(636, 644, 356, 364), depth=(6.0, 6.05))
     base = sc.ki_desc[sc.ki_index[0]]
     for j in range(100):
@@ -286,12 +287,12 @@ def _blob():
     q = np.array([F * c[0] / c[2] + W / 2, F * c[1] / c[2] + H / 2])
     # the predicted octave of the blob's points in this keyframe
     val = math.log2(np.linalg.norm(np.mean(sc.X, axis=0) - C) / np.mean(sc.dmin)) / math.log2(sc.scale) - 0.5
-    idx = r.choice(len(kf.kp), 40, replace=False)
+    idx = r.choice(len(kf.kp), size, replace=False)
     for t in idx:
         kf.kp[t] = (q[0] + r.uniform(-4, 4), q[1] + r.uniform(-4, 4), 31.0, -1.0, 10.0, int(math.floor(val + 0.5)), -1)
         kf.desc[t] = _flip(r, base, int(r.integers(0, 5)))
         kf.mask[t] = True
-    return sc.case("blob", NewPointsAssociationSettings(image_border=BORDER, min_hamming_difference=0))
+    return sc.case(name, NewPointsAssociationSettings(image_border=BORDER, min_hamming_difference=0))
 
 
 def _many_kp(n_kp, name):
@@ -347,8 +348,8 @@ def _no_keyframes():
 def cases():
     """name -> Case, in a fixed order."""
     out = [_base(), _views(), _contend(), _octaves3(), _levels4(), _empty(), _no_keyframes(), _count(1, "n1", 46),
-           _count(64, "n64", 47), _count(65, "n65", 48), _count(257, "n257", 54), _blob(), _many_kp(4096, "kp4096"),
-           _many_kp(4097, "kp4097"), _bad_index()]
+           _count(64, "n64", 47), _count(65, "n65", 48), _count(257, "n257", 54), _blob(40, "blob"), _blob(8, "blob8"),
+           _blob(9, "blob9"), _many_kp(4096, "kp4096"), _many_kp(4097, "kp4097"), _bad_index()]
     return {c.name: c for c in out}
 
 
@@ -448,6 +449,22 @@ def start_mask(c: Case, k: int) -> np.ndarray:
             if int(pt["kc_slot"]) == kf.slot and int(pt["kc_index"]) < len(m):
                 m[int(pt["kc_index"])] = 0
     return m
+
+
+def start_candidates(c: Case, rec, v, k: int) -> np.ndarray:
+    """Per point that went on to keyframe k's descriptor search, the keypoints it can be offered under
+    the starting mask, from the records' (x, y, octave): inside the float32 box, the predicted octave,
+    unassociated, Hamming distance <= max_hamming_distance."""
+    kf = c.kfs[k]
+    passed = np.nonzero(np.isin(v[:, k], [ASSOCIATED, NO_MATCH]))[0]
+    r = np.float32(c.assoc.search_radius)
+    px, py = rec["x"][passed, k][:, None], rec["y"][passed, k][:, None]
+    x, y = kf.kp["x"][None], kf.kp["y"][None]
+    box = (x >= px - r) & (x <= px + r) & (y >= py - r) & (y <= py + r)
+    qd = c.ki_desc[c.points["ki_index"][passed].astype(np.int64)].reshape(-1, 32)
+    d = np.unpackbits(qd[:, None] ^ kf.desc[None], axis=2).sum(2)
+    return (box & (kf.kp["octave"][None] == rec["octave"][passed, k][:, None]) & (start_mask(c, k) != 0)[None] &
+            (d <= c.assoc.max_hamming_distance)).sum(1)
 
 
 def composition_scene():

@@ -60,17 +60,32 @@ def test_local_map_match_matches_oracle(gpu, seed, nt, nq, dup, octaves):
     assert (o >= 0).sum() > nq // (4 * dup)  # the case really associates keypoints
 
 
-def test_local_map_match_conflicts_and_overflow(gpu):
-    """A dense blob of 40 keypoints with near-identical descriptors inside one search box and 200 map
-    points all projecting into it: every point sees > 8 candidates (overflow rescans) and each success
-    changes the next points' results."""
+def start_candidates(qp, qo, qd, kp, desc, radius, md):
+    """Per query, the keypoints it can be offered when every keypoint is unassociated: inside the f32
+    box, the query's octave, Hamming distance <= md."""
+    r = np.float32(radius)
+    x, y = kp["x"][None], kp["y"][None]
+    box = (x >= qp[:, :1] - r) & (x <= qp[:, :1] + r) & (y >= qp[:, 1:] - r) & (y <= qp[:, 1:] + r)
+    d = np.unpackbits(qd[:, None] ^ desc[None], axis=2).sum(2)
+    return (box & (kp["octave"][None] == qo[:, None]) & (d <= md)).sum(1)
+
+
+@pytest.mark.parametrize("blob", [8, 9, 40])
+def test_local_map_match_conflicts_and_overflow(gpu, blob):
+    """A dense blob of keypoints with near-identical descriptors inside one search box and map points
+    all projecting into it, so that each success changes the next points' results.  40 keypoints and
+    200 points: every point sees > 8 candidates (overflow rescans).  8 and 9 keypoints and 70 points
+    (two 64-lane rounds): the kept list exactly full, and the first overflow; there the descriptors
+    are spread wider, so that the points still take keypoints at minHammingDifference 3."""
     rng = np.random.default_rng(7)
-    kp, desc = frame(rng, 1000, cluster=40)
-    desc[:40] = desc[0] ^ (rng.random((40, 32)) < 0.05).astype(np.uint8)
-    nq = 200
+    nq, kflip, qflip = (200, 0.05, 0.03) if blob == 40 else (70, 0.3, 0.1)
+    kp, desc = frame(rng, 1000, cluster=blob)
+    desc[:blob] = desc[0] ^ (rng.random((blob, 32)) < kflip).astype(np.uint8)
     qp = np.float32([640, 360]) + rng.uniform(-2, 2, (nq, 2)).astype(np.float32)
     qo = np.zeros(nq, np.int32)
-    qd = np.repeat(desc[:1], nq, 0) ^ (rng.random((nq, 32)) < 0.03).astype(np.uint8)
+    qd = np.repeat(desc[:1], nq, 0) ^ (rng.random((nq, 32)) < qflip).astype(np.uint8)
+    cand = start_candidates(qp, qo, qd, kp, desc, 8.0, 30)
+    assert (cand == blob).any() if blob < 40 else (cand > 8).all(), np.bincount(cand)
     for mdiff in (0, 1, 3):
         g, gm, o, om = run_both(qp, qo, qd, kp, desc, np.ones(1000, bool), None, 8.0, 30, mdiff)
         assert np.array_equal(g, o) and np.array_equal(gm, om), mdiff

@@ -32,6 +32,8 @@ def test_kernel_equals_host_twin(gpu, host, name):
     assert rec.tobytes() == hrec.tobytes()
     for k in range(len(c.kfs)):
         assert np.array_equal(masks[k], hmasks[k]), (name, k)
+    if name in ("blob8", "blob9"):  # the kept list of 8 exactly full, and its first overflow
+        assert (ac.start_candidates(c, hrec, hv, 0) == int(name[4:])).any()
 
 
 def dev(a):

@@ -120,6 +120,9 @@ def test_coverage(host):
              (np.abs(kp["y"] - rec["y"][p, 0]) <= c.assoc.search_radius) & (kp["octave"] == rec["octave"][p, 0])
              for p in range(100)]
     assert np.median([b.sum() for b in inbox]) >= 30 and (v[:, 0] == ac.ASSOCIATED).sum() >= 30
+    # the kernel's kept list of 8 exactly full, and its first overflow
+    for n, size in (("blob8", 8), ("blob9", 9)):
+        assert (ac.start_candidates(cs[n], host[n][0], host[n][1], 0) == size).any()
 
 
 def test_order_matters(host):
