@@ -260,8 +260,12 @@ mage_status mage_hamming_match(const uint8_t* desc_a, uint32_t n_a, const uint8_
                                uint32_t cap, uint32_t* n);
 
 /* Batched device form: pair p matches A = d_desc_a + p*a_pitch (n_a[p] rows) against
- * B = d_desc_b + p*b_pitch (n_b[p] rows); no masks.  Results per pair at d_out + p*cap,
- * count in d_n[p].  d_n_a / d_n_b are device arrays.  Asynchronous on `stream`. */
+ * B = d_desc_b + p*b_pitch (n_b[p] rows); no masks.  The pitches are in bytes (multiples of 16) and
+ * need not be equal; b_pitch == 0 shares one B set between all pairs (d_n_b still holds one count
+ * per pair).  A pair with a zero count, or with a count above 4096, reports 0.  Results per pair at
+ * d_out + p*cap: d_n[p] is the number of matches found and may exceed cap; only the first cap of
+ * them (ascending A index) are written, and nothing past min(d_n[p], cap) records of a pair's
+ * region is touched.  d_n_a / d_n_b are device arrays of `pairs` counts.  Asynchronous on `stream`. */
 mage_status mage_hamming_match_batch_device(const uint8_t* d_desc_a, int64_t a_pitch,
                                             const uint32_t* d_n_a, const uint8_t* d_desc_b,
                                             int64_t b_pitch, const uint32_t* d_n_b,
@@ -298,11 +302,18 @@ mage_status mage_local_map_match(const float* query_pos, const int32_t* query_oc
                                  const uint8_t* target_desc, uint32_t n_target, uint8_t* mask, float radius,
                                  int32_t max_distance, int32_t min_difference, int32_t* result, int device);
 
-/* Batched device form, one (query set, target set) pair per workgroup: pair p reads
- * query_pitch / target_pitch entries further on (keypoints, positions, 32-byte descriptors),
- * counts from d_n_query[p] / d_n_target[p]; no masks.  d_scratch: pairs x query_pitch int32.
- * Results at d_out + p*cap, count in d_n[p]; bit 0 of *d_status is set when a target set exceeds
- * 4096 (that pair reports 0 matches).  Asynchronous on `stream`. */
+/* Batched device form, one (query set, target set) pair per workgroup (several below 128 pairs):
+ * pair p reads query_pitch / target_pitch entries further on (keypoints, positions, 32-byte
+ * descriptors; the two pitches need not be equal), counts from d_n_query[p] / d_n_target[p]; no
+ * masks.  d_query_pos may be NULL (the keypoints' own positions); otherwise pair p's overrides are
+ * at d_query_pos + 2*p*query_pitch floats.  d_scratch: pairs x query_pitch int32.  Results at
+ * d_out + p*cap: d_n[p] is the number of matches found and may exceed cap; only the first cap of
+ * them (query order) are written, and nothing past min(d_n[p], cap) records of a pair's region is
+ * touched.  A pair without queries reports 0 and is not checked any further; one without targets
+ * reports 0.  A pair with queries whose target set exceeds 4096 ORs bit 0 into *d_status (zeroed
+ * by the caller); otherwise one with a count above its pitch (n_query > query_pitch or n_target >
+ * target_pitch) ORs bit 1 into it: one bit per offending pair, bit 0 taking precedence.  Such a
+ * pair reports 0 matches and the other pairs are unaffected.  Asynchronous on `stream`. */
 mage_status mage_radius_match_batch_device(const mage_keypoint* d_query_kp, const float* d_query_pos,
                                            const uint8_t* d_query_desc, int64_t query_pitch,
                                            const uint32_t* d_n_query, const mage_keypoint* d_target_kp,
@@ -366,8 +377,12 @@ mage_status mage_indexed_match(mage_bow* bow, const uint8_t* desc_a, uint32_t n_
 
 /* Batched device form, one (A, B) pair per workgroup, leaves precomputed (e.g. by
  * mage_bow_find_leaves_device): pair p reads a_pitch / b_pitch entries further on (descriptors,
- * leaves, optional masks), counts d_n_a[p] / d_n_b[p].  Results at d_out + p*cap, count in d_n[p];
- * bit 0 of *d_status is set when a side exceeds 4096 (that pair reports 0).  Asynchronous. */
+ * leaves, optional masks; either mask may be NULL on its own, the pitches need not be equal), counts
+ * d_n_a[p] / d_n_b[p]; a pair with a zero (masked) count on either side reports 0.  Results at
+ * d_out + p*cap: d_n[p] is the number of matches found and may exceed cap; only the first cap of
+ * them (ascending A index) are written, and nothing past min(d_n[p], cap) records of a pair's
+ * region is touched.  Bit 0 of *d_status (zeroed by the caller) is set when a side exceeds 4096;
+ * that pair reports 0 and the other pairs are unaffected.  Asynchronous. */
 mage_status mage_indexed_match_batch_device(const uint8_t* d_desc_a, const uint32_t* d_leaf_a, const uint8_t* d_mask_a,
                                             int64_t a_pitch, const uint32_t* d_n_a, const uint8_t* d_desc_b,
                                             const uint32_t* d_leaf_b, const uint8_t* d_mask_b, int64_t b_pitch,

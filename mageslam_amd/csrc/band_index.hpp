@@ -15,9 +15,14 @@ __device__ __forceinline__ unsigned orderable(float v)
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+// -0.0f takes the key of +0.0f: orderable() puts it one below, but the box test compares floats,
+// where the two are equal, so a target at -0.0 belongs to a band whose edge is +0.0 and the other
+// way round.  Decided on the bits (no dependence on the floating-point mode).
 __device__ __forceinline__ unsigned long long band_key(int octave, float y, unsigned idx)
 {
-    return ((unsigned long long)(octave & 0xFF) << 56) | ((unsigned long long)orderable(y) << 24) | idx;
+    const unsigned u = __float_as_uint(y);
+    const unsigned oy = u == 0x80000000u ? 0x80000000u : orderable(y);  // orderable(+0.0f) = 0x80000000
+    return ((unsigned long long)(octave & 0xFF) << 56) | ((unsigned long long)oy << 24) | idx;
 }
 
 // first position in keys[0, n) (ascending) with keys[pos] >= k

@@ -268,3 +268,79 @@ def test_online_bow_query_edges(gpu, oracle, frames):
         for m in (1, 2, 10):
             assert g.QueryUnknownImage(q, m) == o.QueryUnknownImage(q, m)
     assert len(g.QueryUnknownImage(descs[0], 1)) == 1
+
+
+# counts (n_a, n_b) of test_indexed_match_batch_pitches_empty_pairs_status
+BATCH_COUNTS = [(300, 2049), (0, 700), (700, 0), (1025, 2047), (1, 1)]
+# the second layout: an unstaged B set at pair 1, a B count above the limit at pair 2
+BATCH_COUNTS_LARGE = [(300, 2049), (1025, 3000), (700, 4097), (1, 1)]
+
+
+def batch_sets():
+    """One (A, B) descriptor pair per entry of BATCH_COUNTS, then per entry of BATCH_COUNTS_LARGE; a
+    side with a zero count still holds 300 matchable rows."""
+    from match_cases import match_sets
+
+    counts = BATCH_COUNTS + BATCH_COUNTS_LARGE
+    return [match_sets(max(na, 300), max(nb, 300), 50 + p) for p, (na, nb) in enumerate(counts)]
+
+
+def batch_tree(sets):
+    return synth.bow_tree(np.concatenate([sets[0][0], sets[3][0], sets[0][1][:500]]))
+
+
+def test_indexed_match_batch_pitches_empty_pairs_status(gpu, oracle):
+    """indexed_match_kernel at pair > 0 with a_pitch != b_pitch and a mask on the B side only (80 % of
+    the entries kept).  First layout (b_pitch 2100): pairs with a zero count on either side over
+    matchable rows, and B sets of 2049 and 2047 rows, whose masked counts stay below the 2048
+    descriptors staged in LDS.  Second layout (b_pitch 4100): pair 1 has 3000 B rows and a masked
+    count above 2048 (asserted), so it takes the unstaged path that reads B's descriptors from
+    global memory at its pair offset; pair 2 has n_b = 4097, which sets bit 0 of the status word and
+    reports 0 while its neighbours stay exact.  Outputs are prefilled with 0xA5: every byte past a
+    pair's matches must still hold it.  Leaves come from the oracle's descent (find_leaves has its
+    own test), so only the matcher is under test."""
+    import torch
+
+    from match_cases import CANARY, assert_regions
+
+    all_sets = batch_sets()
+    tree = batch_tree(all_sets)
+    empty = np.zeros(0, DM_DTYPE)
+
+    def run(sets, counts, a_pitch, b_pitch):
+        """-> (oracle results, status, masked B counts); the device results are checked here."""
+        pairs = len(sets)
+        rng = np.random.default_rng(77)
+        DA = np.zeros((pairs, a_pitch, 32), np.uint8)
+        DB = np.zeros((pairs, b_pitch, 32), np.uint8)
+        MB = np.zeros((pairs, b_pitch), np.uint8)
+        for p, (a, b) in enumerate(sets):
+            DA[p], DB[p] = np.resize(a, (a_pitch, 32)), np.resize(b, (b_pitch, 32))
+            MB[p] = rng.random(b_pitch) < 0.8
+        LA = oracle.bow_find_leaves(tree, DA.reshape(-1, 32)).astype(np.int32).reshape(pairs, a_pitch)
+        LB = oracle.bow_find_leaves(tree, DB.reshape(-1, 32)).astype(np.int32).reshape(pairs, b_pitch)
+        exp = []
+        for p, (na, nb) in enumerate(counts):
+            ok = 0 < na <= 4096 and 0 < nb <= 4096
+            exp.append(oracle.indexed_match(tree, DA[p, :na], DB[p, :nb], None, MB[p, :nb]) if ok else empty)
+        dev = "cuda"
+        tDA, tDB, tLA, tLB, tMB = (torch.from_numpy(x).to(dev) for x in (DA, DB, LA, LB, MB))
+        tna = torch.tensor([c[0] for c in counts], dtype=torch.int32, device=dev)
+        tnb = torch.tensor([c[1] for c in counts], dtype=torch.int32, device=dev)
+        out = torch.full((pairs, a_pitch * 16), CANARY, dtype=torch.uint8, device=dev)
+        nout = torch.full((pairs,), -1, dtype=torch.int32, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        bow.indexed_match_batch_device(tDA, tLA, None, a_pitch, tna, tDB, tLB, tMB, b_pitch, tnb, pairs, 30, 1, out,
+                                       a_pitch, nout, status)
+        torch.cuda.synchronize()
+        assert_regions(out.cpu().numpy(), nout.cpu().numpy(), a_pitch, exp, counts)
+        return exp, int(status.item()), [int(MB[p, :nb].sum()) for p, (_, nb) in enumerate(counts)]
+
+    k = len(BATCH_COUNTS)
+    exp, status, kept = run(all_sets[:k], BATCH_COUNTS, 1100, 2100)
+    assert status == 0
+    assert all(len(e) > 0 for e, c in zip(exp, BATCH_COUNTS) if min(c))
+    exp, status, kept = run(all_sets[k:], BATCH_COUNTS_LARGE, 1100, 4100)
+    assert status == 1
+    assert kept[1] > 2048  # pair 1 is not staged in LDS
+    assert len(exp[0]) > 0 and len(exp[1]) > 0 and len(exp[2]) == 0 and len(exp[3]) > 0
