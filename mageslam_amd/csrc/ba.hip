@@ -9,8 +9,8 @@
 //   point_linearize   thread/point: errors of its edges (kept per edge, as g2o keeps _error),
 //                     robust chi2, Hll, bl and Hpl_e = J_pose^T w J_point per edge
 //   cam_linearize     workgroup/camera: Hpp, bp (recomputes J_pose; no per-edge 6x6 in HBM)
-//   trial loop (<= 10; one pinned 128-byte control-block readback per trial decides accept /
-//   reject on the host):
+//   trial loop (<= 10; one readback of the host-mapped control block (BaCtl) per trial decides
+//   accept / reject on the host):
 //     edge_schur      thread/point-edge: Dinv_p = (Hll + lambda I)^-1, db = Dinv bl (first edge
 //                     of each point), Z_e = Hpl_e Dinv_p (6x3) for every edge
 //     schur_chunks    per covisible camera pair (h1 <= h2) the Schur products (e1, e2) of its
@@ -85,6 +85,23 @@ struct LmDev {
     int cur_next;
     int accept;
 };
+
+// The control block: host memory the kernels write directly (pinned, coherent, mapped), read by
+// the host at every decision after a completion wait on `seq`.  Every field has one writer, and a
+// reduce3 launch with no sums to report (the outlier-only reduction) writes none, so no launch
+// writes a field another consumer reads.  What one trial writes lies within two 64-byte lines.
+struct BaCtl {
+    struct Sums {
+        double chi2, scale, maxd;
+    };
+    Sums lin;            // linearize_finish: chi2 and max diagonal of the linearisation (computeLambdaInit)
+    Sums trial;          // reduce3: chi2 of the trial state and computeScale
+    OutlierCtl outlier;  // reduce3: the post-pass sums, the trial's Cholesky failure flag and counts
+    double chi2_cur;     // reduce3: chi2 of the linearised (current) state
+    double lam_next;     // reduce3: the device's lambda for the next trial (LmDev::lam_next)
+    volatile unsigned seq;  // completion word of the last launch that reports to the host, written last
+};
+static_assert(sizeof(BaCtl) <= 128, "control block layout");
 
 template <int N>
 __device__ __forceinline__ void group_sum(double (&v)[N])
@@ -546,7 +563,7 @@ __global__ __launch_bounds__(BA_THREADS) void linearize_kernel(Problem pb, State
 }
 
 // After the linearisation (one workgroup): Hpp / bp of every free camera from its chunk partials,
-// and out[0] = sum of the points' robust chi2, out[2] = max diagonal entry over Hll and Hpp
+// and out->chi2 = sum of the points' robust chi2, out->maxd = max diagonal entry over Hll and Hpp
 // (computeLambdaInit), with the fixed-order tree of reduce3.
 __global__ __launch_bounds__(1024) void linearize_finish(int nb, const int* __restrict__ cam_of_block,
                                                          const double* __restrict__ part,
@@ -555,7 +572,7 @@ __global__ __launch_bounds__(1024) void linearize_finish(int nb, const int* __re
                                                          const Tether* __restrict__ teth, int nt,
                                                          const double* __restrict__ tout,
                                                          double* __restrict__ Hpp, double* __restrict__ bp,
-                                                         double* __restrict__ out)
+                                                         BaCtl::Sums* __restrict__ out)
 {
     __shared__ double cams[MAX_FREE_CAMS][27];
     __shared__ double sa[1024], sm[1024];
@@ -618,26 +635,84 @@ __global__ __launch_bounds__(1024) void linearize_finish(int nb, const int* __re
         __syncthreads();
     }
     if (tid == 0) {
-        out[0] = sa[0];
-        out[1] = 0;
-        out[2] = sm[0];
+        out->chi2 = sa[0];
+        out->scale = 0;
+        out->maxd = sm[0];
     }
 }
 
 
-// Fixed-order reduction of two sum arrays and one max array into out[0..2], a third sum array into
-// outc[0] (the linearisation's chi2), and with ns > 0 the post-pass's per-block (sum, count)
-// partials of its ns states into ctl->osum.
-__global__ __launch_bounds__(1024) void reduce3(const double* __restrict__ a, int na,
-                                                const double* __restrict__ b, int nb,
-                                                const double* __restrict__ m, int nm,
-                                                double* __restrict__ out,
-                                                const double* __restrict__ c, int nc, double* __restrict__ outc,
-                                                const double* __restrict__ opart, int oblocks, int ns,
-                                                OutlierCtl* __restrict__ ctl, LiveCtl* __restrict__ live,
-                                                unsigned* __restrict__ seq_out, unsigned seq,
-                                                LmDev* __restrict__ lm, double lam, double ni, int cur,
-                                                double cur_chi, double* __restrict__ lam_out)
+// Fixed-order reduction of two sum arrays and one max array into ctl->trial (a trial's), a third into
+// ctl->chi2_cur (the linearisation's chi2), and with ns > 0 the post-pass's per-block (sum, count)
+// partials of its ns states into ctl->outlier.osum.
+struct ReduceArgs {
+    const double* a;  // sum array -> ctl->trial.chi2
+    int na;
+    const double* b;  // sum array -> ctl->trial.scale
+    int nb;
+    const double* m;  // max array -> ctl->trial.maxd
+    int nm;
+    int trial;  // a, b and m are a trial's: report them in ctl->trial (0: nothing to report)
+    const double* c;   // sum array -> ctl->chi2_cur (written when nc > 0)
+    int nc;
+    const double* opart;  // [2 ns][oblocks] post-pass block partials
+    int oblocks, ns;
+    BaCtl* ctl;
+    LiveCtl* live;
+    unsigned seq;
+    LmDev* lm;  // non-null: take the trial's LM decision from lam, ni, cur, cur_chi
+    double lam, ni;
+    int cur;
+    double cur_chi;
+};
+// reduce3's report by thread 0: red = the seven sums and the max.  (A function for the sake of its
+// __restrict__ parameters: the trial counters are read with scalar loads between the stores to the
+// host block; without them every such read waits for the stores before it.)
+__device__ __forceinline__ void reduce3_report(const ReduceArgs& r, const double (&red)[8], BaCtl* __restrict__ ctl,
+                                               LiveCtl* __restrict__ live)
+{
+    if (r.trial) ctl->trial = BaCtl::Sums{red[0], red[1], red[7]};
+    if (r.nc > 0) ctl->chi2_cur = red[2];
+    for (int k = 0; k < r.ns; k++) {
+        ctl->outlier.osum[k][0] = red[3 + 2 * k];
+        ctl->outlier.osum[k][1] = red[4 + 2 * k];
+    }
+    if (r.lm) {
+        // the trial's LM decision (see LmDev); the chi of the current state is the
+        // linearisation's (reduced here) unless the host passed it
+        const double tempChi = live->fail ? __DBL_MAX__ : red[0];
+        const double currentChi = isnan(r.cur_chi) ? red[2] : r.cur_chi;
+        double rho = currentChi - tempChi;
+        const double scale = red[1] + 1e-3;
+        rho /= scale;
+        const bool acc = rho > 0 && isfinite(tempChi);
+        double ln;
+        if (acc) {
+            double alpha = 1. - pow(2 * rho - 1, 3.0);
+            alpha = fmin(alpha, 2. / 3.);
+            ln = r.lam * fmax(1. / 3., alpha);
+        } else {
+            ln = r.lam * r.ni;
+        }
+        r.lm->lam_next = ln;
+        r.lm->cur_next = acc ? 1 - r.cur : r.cur;
+        r.lm->accept = acc ? 1 : 0;
+        ctl->lam_next = ln;
+    }
+    // the trial's counters to the host block, and zero for the next trial
+    ctl->outlier.fail = live->fail;
+    ctl->outlier.count[0] = live->count[0];
+    ctl->outlier.count[1] = live->count[1];
+    live->fail = 0;
+    live->count[0] = 0;
+    live->count[1] = 0;
+    // completion word for the host's spin-wait: every result above reaches host memory first
+    // (drained plain stores before the word measured the same, tools/ablate_ba.py)
+    __threadfence_system();
+    ctl->seq = r.seq;
+}
+
+__global__ __launch_bounds__(1024) void reduce3(ReduceArgs r)
 {
     // the seven sums in one pass (strided per thread, fixed order), one reduce-scatter per wave,
     // then the 16 wave partials in order; the max separately (only linearize_finish's callers
@@ -651,15 +726,15 @@ __global__ __launch_bounds__(1024) void reduce3(const double* __restrict__ a, in
     // first loads of every array issued together (one array after another waited on each array's
     // loads in turn: 7 dependent memory round trips per launch on C3, 6.9 -> 6.0 us in
     // tools/ablate_ba.py); the tails past them follow.
-    const double* segp[7] = {a, b, c, opart, opart + oblocks, opart + 2 * oblocks, opart + 3 * oblocks};
-    const int segn[7] = {na, nb, nc, ns > 0 ? oblocks : 0, ns > 0 ? oblocks : 0, ns > 1 ? oblocks : 0,
-                         ns > 1 ? oblocks : 0};
+    const int ob = r.oblocks;
+    const double* segp[7] = {r.a, r.b, r.c, r.opart, r.opart + ob, r.opart + 2 * ob, r.opart + 3 * ob};
+    const int segn[7] = {r.na, r.nb, r.nc, r.ns > 0 ? ob : 0, r.ns > 0 ? ob : 0, r.ns > 1 ? ob : 0, r.ns > 1 ? ob : 0};
     constexpr int J3 = 6, J4 = 1;  // first loads per thread: point / camera arrays, block partials
     // branch-free: every load reads a valid address (an absent array reads the live block) and a
     // select drops what lies past the array, so no load waits inside a branch
     auto first = [&](int k, int j) {
         const int i = tid + 1024 * j, n = segn[k];
-        const double* src = n > 0 ? segp[k] : reinterpret_cast<const double*>(live);
+        const double* src = n > 0 ? segp[k] : reinterpret_cast<const double*>(r.live);
         const double x = src[min(i, max(n - 1, 0))];
         return i < n ? x : 0.0;
     };
@@ -683,7 +758,7 @@ __global__ __launch_bounds__(1024) void reduce3(const double* __restrict__ a, in
 #pragma unroll
     for (int k = 0; k < 7; k++)
         for (int i = tid + 1024 * (k < 3 ? J3 : J4); i < segn[k]; i += 1024) v[k] += segp[k][i];
-    for (int i = tid; i < nm; i += 1024) vm = fmax(vm, m[i]);
+    for (int i = tid; i < r.nm; i += 1024) vm = fmax(vm, r.m[i]);
     const int e = reduce_scatter<7, kWave>(v, lane);
     if (e >= 0) red[wave][e] = v[0];
     for (int off = 32; off > 0; off >>= 1) vm = fmax(vm, __shfl_xor(vm, off));
@@ -699,49 +774,7 @@ __global__ __launch_bounds__(1024) void reduce3(const double* __restrict__ a, in
         red[0][7] = t;
     }
     __syncthreads();
-    if (tid == 0) {
-        out[0] = red[0][0];
-        out[1] = red[0][1];
-        out[2] = red[0][7];
-        if (nc > 0) outc[0] = red[0][2];
-        for (int k = 0; k < ns; k++) {
-            ctl->osum[k][0] = red[0][3 + 2 * k];
-            ctl->osum[k][1] = red[0][4 + 2 * k];
-        }
-        if (lm) {
-            // the trial's LM decision (see LmDev); the chi of the current state is the
-            // linearisation's (reduced here) unless the host passed it
-            const double tempChi = live->fail ? __DBL_MAX__ : red[0][0];
-            const double currentChi = isnan(cur_chi) ? red[0][2] : cur_chi;
-            double rho = currentChi - tempChi;
-            const double scale = red[0][1] + 1e-3;
-            rho /= scale;
-            const bool acc = rho > 0 && isfinite(tempChi);
-            double ln;
-            if (acc) {
-                double alpha = 1. - pow(2 * rho - 1, 3.0);
-                alpha = fmin(alpha, 2. / 3.);
-                ln = lam * fmax(1. / 3., alpha);
-            } else {
-                ln = lam * ni;
-            }
-            lm->lam_next = ln;
-            lm->cur_next = acc ? 1 - cur : cur;
-            lm->accept = acc ? 1 : 0;
-            lam_out[0] = ln;
-        }
-        // the trial's counters to the host block, and zero for the next trial
-        ctl->fail = live->fail;
-        ctl->count[0] = live->count[0];
-        ctl->count[1] = live->count[1];
-        live->fail = 0;
-        live->count[0] = 0;
-        live->count[1] = 0;
-        // completion word for the host's spin-wait: every result above reaches host memory first
-        // (drained plain stores before the word measured the same, tools/ablate_ba.py)
-        __threadfence_system();
-        *reinterpret_cast<volatile unsigned*>(seq_out) = seq;
-    }
+    if (tid == 0) reduce3_report(r, red[0], r.ctl, r.live);
 }
 
 
@@ -1842,13 +1875,13 @@ __global__ __launch_bounds__(BA_THREADS) void drop_edges(const int* __restrict__
 // The initialisation summary into mapped host memory, completion word last (the host spins on it
 // instead of a D2H copy + stream synchronisation).
 __global__ __launch_bounds__(1024) void summary_out(const int* __restrict__ sum, int n, int* __restrict__ out,
-                                                    unsigned* __restrict__ seq_out, unsigned seq)
+                                                    BaCtl* __restrict__ ctl, unsigned seq)
 {
     for (int i = threadIdx.x; i < n; i += 1024) out[i] = sum[i];
     __syncthreads();
     if (threadIdx.x == 0) {
         __threadfence_system();
-        *reinterpret_cast<volatile unsigned*>(seq_out) = seq;
+        ctl->seq = seq;
     }
 }
 
@@ -2519,7 +2552,7 @@ __global__ __launch_bounds__(64) void sc_pair_fill(int nb, int PW, const uint32_
 // host's arithmetic of BundlerLib.cpp:457-465, in the same order, no contraction), per point the
 // position as float; the completion word is written last.
 __global__ __launch_bounds__(1024) void export_state(State s, int C, int P, float* __restrict__ out,
-                                                     unsigned* __restrict__ seq_out, unsigned seq)
+                                                     BaCtl* __restrict__ ctl, unsigned seq)
 {
     float* pos3 = out;
     float* r9 = out + 3 * C;
@@ -2550,7 +2583,7 @@ __global__ __launch_bounds__(1024) void export_state(State s, int C, int P, floa
     __syncthreads();
     if (threadIdx.x == 0) {
         __threadfence_system();
-        *reinterpret_cast<volatile unsigned*>(seq_out) = seq;
+        ctl->seq = seq;
     }
 }
 
@@ -2616,6 +2649,39 @@ static void chol_tile_table(int mt, const SchurPair* pairs, int npairs, std::vec
 }
 static_assert(CT_TW * CT_TPW >= CT_MAXT * (CT_MAXT + 1) / 2 - 1, "every tile but (0, 0) has a slot");
 
+// A buffer (DeviceBuffer, PinnedBuffer, MappedBuffer) that joins its owner's list when constructed:
+// BundleAdjuster::release() walks the list, so a buffer is declared once and named nowhere else.
+// Intrusive (the head is a member of the owner): no allocation per instance.
+struct BufferNode {
+    BufferNode* next;
+    void (*drop)(BufferNode*, bool idle);  // retire into the block cache when idle, else free
+};
+template <typename Buf>
+struct Listed : Buf, BufferNode {
+    explicit Listed(BufferNode*& head)
+        : BufferNode{head, [](BufferNode* b, bool idle) {
+                         Buf* buf = static_cast<Listed*>(b);
+                         idle ? buf->retire() : buf->release();
+                     }}
+    {
+        head = this;
+    }
+    Listed(const Listed&) = delete;
+    Listed& operator=(const Listed&) = delete;
+};
+// Device buffer of T: reserves in elements and passes as T* (a kernel argument, a base for offsets).
+template <typename T>
+struct DeviceArray : Listed<DeviceBuffer> {
+    DeviceArray(BufferNode*& head) : Listed<DeviceBuffer>(head) {}  // implicit: T a[2]{head, head}
+    operator T*() const { return static_cast<T*>(ptr); }
+    mage_status reserve(size_t n) { return DeviceBuffer::reserve(n * sizeof(T)); }
+};
+// launch() takes its arguments by value: an array passes as its pointer
+template <typename T>
+T* launch_arg(const DeviceArray<T>& a) { return a; }
+template <typename T>
+const T& launch_arg(const T& v) { return v; }
+
 struct BundleAdjuster {
     int device = 0;
     bool points_fixed = false;
@@ -2629,28 +2695,30 @@ struct BundleAdjuster {
     bool useless = false, state_on_device = false, host_state_stale = false, err_initialized = false;
     int iteration = 0;
     double user_lambda = 0, lambda = 0, ni = 2, huber = 0;
-    // a linearisation launched at the end of the previous step for the next one (see step())
-    bool eager = false, eager_init = false;
-    double eager_huber = 0, eager_lambda = 0;
-    int eager_cur = -1;
+    // A linearisation already on the stream for the next lm_solve: launched by initialize(), at
+    // the end of step() (see there) or behind a trial's reduce3 (spec_lin), and what it linearised.
+    // lm_solve takes it up, and step() queues no other, only while all of it still holds.
+    struct QueuedLin {
+        bool valid = false;
+        bool init = false;  // with computeLambdaInit's reduction (linearize_finish); no lambda then
+        double huber = 0, lambda = 0;
+        int cur = -1;  // the state buffer
+        bool matches(bool init_, double huber_, double lambda_, int cur_) const
+        {
+            return valid && init == init_ && huber == huber_ && cur == cur_ && (init_ || lambda == lambda_);
+        }
+        void invalidate() { valid = false; }
+    } queued;
     int n = 0, np = 0;  // 6 * cameras in the system, padded to a multiple of 16
     int npairs = 0, n_slots = 0, n_sblocks = 0, n_sfinish = 0;  // Schur pairs, partial slots, blocks, schur_finish pairs
     std::vector<int> camh, ptfree, cam_of_block;
     hipStream_t st = nullptr;
-    // Control block read back at every host decision (one pinned copy per synchronisation):
-    // doubles [0,3) linearisation chi2 / max diag, [3,6) trial, then the outlier pass's
-    // OutlierCtl (sums, Cholesky failure flag, counts, ticket).
-    static constexpr int CTL_DOUBLES = 16, CTL_OUTLIER = 6, CTL_SCRATCH = 12, CTL_LMNEXT = 13, CTL_SEQ = 15;
-    static_assert(CTL_OUTLIER * 8 + sizeof(OutlierCtl) <= CTL_SCRATCH * 8, "control block layout");
-    // The control block is host memory the kernels write directly (pinned, coherent, mapped):
-    // h_ctl on the host, h_ctl_dev in kernels; a trial's results need only the stream sync.
-    double* h_ctl = nullptr;
-    double* h_ctl_dev = nullptr;
-    size_t ctl_bytes = 0;  // the block's real size (a cached block may be larger than CTL_DOUBLES)
-    OutlierCtl* d_octl() const { return reinterpret_cast<OutlierCtl*>(h_ctl_dev + CTL_OUTLIER); }
-    const OutlierCtl& h_octl() const { return *reinterpret_cast<const OutlierCtl*>(h_ctl + CTL_OUTLIER); }
-    LiveCtl* d_live() const { return reinterpret_cast<LiveCtl*>(d_livebuf.ptr); }
-    int* d_failp() const { return &d_live()->fail; }
+    // Every buffer lists itself here when constructed (see Listed): release() names none.
+    BufferNode* bufs = nullptr;
+    // The control block (BaCtl): ctl() on the host, d_ctl() in kernels.
+    Listed<MappedBuffer> ctl_buf{bufs};
+    const BaCtl& ctl() const { return *ctl_buf.host<BaCtl>(); }
+    BaCtl* d_ctl() const { return ctl_buf.device<BaCtl>(); }
     mage_status read_ctl()
     {
         MAGE_HIP(hipStreamSynchronize(st));
@@ -2660,10 +2728,9 @@ struct BundleAdjuster {
     // stream sync costs ~10-20 us of wake-up per LM trial); after 2 ms fall back to the sync,
     // which also reports a failed launch
     unsigned seq_counter = 0;
-    unsigned* seq_dev() const { return reinterpret_cast<unsigned*>(h_ctl_dev + CTL_SEQ); }
     mage_status wait_seq(unsigned seq)
     {
-        volatile unsigned* f = reinterpret_cast<volatile unsigned*>(h_ctl + CTL_SEQ);
+        const volatile unsigned* f = &ctl().seq;
         const auto t0 = std::chrono::steady_clock::now();
         while (*f != seq) {
             if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) {
@@ -2675,20 +2742,40 @@ struct BundleAdjuster {
         std::atomic_thread_fence(std::memory_order_acquire);
         return MAGE_OK;
     }
-    int ctl_fail() const { return h_octl().fail; }
     int cur = 0;  // which state buffer holds the current estimate
     // device buffers
-    DeviceBuffer d_q[2], d_t[2], d_p[2], d_camk, d_camh, d_ptfree, d_uv, d_ecam, d_ept, d_info,
-        d_pstart, d_pedges, d_pe, d_cstart, d_cedges, d_cpt, d_active, d_err, d_Hll, d_bl, d_Hpl, d_Hpp,
-        d_bp, d_S, d_rhs, d_x, d_chi, d_maxd, d_scale, d_red, d_lm, d_osum, d_camblk,
-        d_ptcnt, d_plist, d_pcnt, d_skeys, d_svals, d_kb, d_chist, d_kdst, d_rblk, d_sbits, d_srank, d_Z, d_campart, d_teth, d_tout, d_ptlist, d_sentries, d_spairs, d_schunks, d_spart,
-        d_sfinish, d_epos, d_chi_lin, d_livebuf, d_removed, d_camflag, d_ikeys, d_ivals, d_isum, d_iacc, d_ctab, d_csort_tmp;
+    DeviceArray<double> d_q[2]{bufs, bufs}, d_t[2]{bufs, bufs}, d_p[2]{bufs, bufs}, d_camk{bufs},
+        d_err{bufs}, d_Hll{bufs}, d_bl{bufs}, d_Hpl{bufs}, d_Hpp{bufs}, d_bp{bufs}, d_S{bufs},
+        d_rhs{bufs}, d_x{bufs}, d_chi{bufs}, d_chi_lin{bufs}, d_maxd{bufs}, d_scale{bufs},
+        d_osum{bufs}, d_Z{bufs}, d_campart{bufs}, d_tout{bufs}, d_spart{bufs};
+    DeviceArray<int> d_camh{bufs}, d_ptfree{bufs}, d_ecam{bufs}, d_ept{bufs}, d_pstart{bufs},
+        d_pedges{bufs}, d_cstart{bufs}, d_cedges{bufs}, d_cpt{bufs}, d_epos{bufs}, d_camblk{bufs},
+        d_ptcnt{bufs}, d_kb{bufs}, d_chist{bufs}, d_kdst{bufs}, d_rblk{bufs}, d_srank{bufs},
+        d_ptlist{bufs}, d_sfinish{bufs}, d_ivals{bufs};
+    DeviceArray<float> d_uv{bufs}, d_info{bufs};
+    DeviceArray<unsigned char> d_active{bufs}, d_removed{bufs}, d_camflag{bufs};
+    DeviceArray<int4> d_pe{bufs};
+    DeviceArray<int2> d_plist{bufs}, d_sentries{bufs};
+    DeviceArray<uint32_t> d_sbits{bufs};
+    DeviceArray<uint16_t> d_ctab{bufs};
+    DeviceArray<Tether> d_teth{bufs};
+    DeviceArray<SchurPair> d_spairs{bufs};
+    DeviceArray<SchurChunk> d_schunks{bufs};
+    DeviceArray<LmDev> d_lm{bufs};
+    DeviceArray<LiveCtl> d_live{bufs};
+    // packed: several arrays in one allocation (laid out where they are reserved)
+    DeviceArray<int> d_pcnt{bufs}, d_iacc{bufs}, d_isum{bufs};
+    DeviceArray<unsigned> d_ikeys{bufs};
+    DeviceArray<uint16_t> d_skeys{bufs};
+    DeviceArray<unsigned long long> d_svals{bufs};
+    DeviceArray<char> d_csort_tmp{bufs};
+    int* d_failp() const { return &static_cast<LiveCtl*>(d_live)->fail; }
     bool iacc_clean = false;  // d_iacc is all zero (see initialize())
     // outlier lists of the speculative / final post-pass (2 x E entries), written by the kernels
     // straight into host memory: the host sorts and returns them after the completion wait
-    MappedBuffer h_olist;
-    PinnedBuffer h_kb;    // per-pair list bounds read back by build_product_lists
-    MappedBuffer h_isum;  // the device initialisation's summary (init_scan etc., INIT_HDR layout)
+    Listed<MappedBuffer> h_olist{bufs};
+    Listed<PinnedBuffer> h_kb{bufs};    // per-pair list bounds read back by build_product_lists
+    Listed<MappedBuffer> h_isum{bufs};  // the device initialisation's summary (init_scan etc., INIT_HDR layout)
     std::vector<int> camcnt;  // active observation edges per camera (host-side bookkeeping)
     int n_entries = 0;  // point-CSR entries (active edges at initialisation)
     int nb_free = 0;    // cameras in the reduced system
@@ -2696,63 +2783,55 @@ struct BundleAdjuster {
 
     static int group_grid(int items) { return (int)(((long long)items * PG + BA_THREADS - 1) / BA_THREADS); }
 
+    // every launch of the BA: mage::launch with the arrays passed as their device pointers
+    template <typename F, typename... Args>
+    void launch(const char* tag, F kernel, dim3 grid, dim3 block, uint32_t shmem, hipStream_t s, const Args&... args)
+    {
+        mage::launch(tag, kernel, grid, block, shmem, s, launch_arg(args)...);
+    }
+    // reserve(n) of each (array, elements) pair in turn; the first failure's status
+    template <typename T, typename... Rest>
+    static mage_status reserve_all(DeviceArray<T>& a, size_t n, Rest&&... rest)
+    {
+        mage_status r = a.reserve(n);
+        if constexpr (sizeof...(rest) > 0)
+            if (r == MAGE_OK) r = reserve_all(rest...);
+        return r;
+    }
+
     Problem problem() const
     {
         Problem pb;
         pb.C = C;
         pb.P = P;
-        pb.camk = d_camk.as<double>();
-        pb.camh = d_camh.as<int>();
-        pb.ptfree = d_ptfree.as<int>();
-        pb.uv = d_uv.as<float>();
-        pb.ecam = d_ecam.as<int>();
-        pb.ept = d_ept.as<int>();
-        pb.info = d_info.as<float>();
-        pb.active = d_active.as<unsigned char>();
-        pb.pstart = d_pstart.as<int>();
-        pb.pedges = d_pedges.as<int>();
-        pb.cstart = d_cstart.as<int>();
-        pb.cedges = d_cedges.as<int>();
-        pb.cpt = d_cpt.as<int>();
-        pb.epos = d_epos.as<int>();
-        pb.pe = d_pe.as<int4>();
+        pb.camk = d_camk;
+        pb.camh = d_camh;
+        pb.ptfree = d_ptfree;
+        pb.uv = d_uv;
+        pb.ecam = d_ecam;
+        pb.ept = d_ept;
+        pb.info = d_info;
+        pb.active = d_active;
+        pb.pstart = d_pstart;
+        pb.pedges = d_pedges;
+        pb.cstart = d_cstart;
+        pb.cedges = d_cedges;
+        pb.cpt = d_cpt;
+        pb.epos = d_epos;
+        pb.pe = d_pe;
         pb.ecsr = n_entries;
         pb.huber = huber;
         return pb;
     }
-    State state(int i) const { return State{d_q[i].as<double>(), d_t[i].as<double>(), d_p[i].as<double>()}; }
+    State state(int i) const { return State{d_q[i], d_t[i], d_p[i]}; }
 
     void release()
     {
         // an eager linearisation may still be running; only blocks of a synchronised stream are
-        // idle and go to the block cache, after a failed synchronisation everything is freed
+        // idle and go to the block cache (common.hpp), after a failed synchronisation everything
+        // is freed
         const bool idle = !st || hipStreamSynchronize(st) == hipSuccess;
-        for (auto* b : {&d_q[0], &d_q[1], &d_t[0], &d_t[1], &d_p[0], &d_p[1], &d_camk, &d_camh, &d_ptfree,
-                        &d_uv, &d_ecam, &d_ept, &d_info, &d_pstart, &d_pedges, &d_pe, &d_cstart, &d_cedges, &d_cpt,
-                        &d_active, &d_err, &d_Hll, &d_bl, &d_Hpl, &d_Hpp, &d_bp, &d_S, &d_rhs,
-                        &d_x, &d_chi, &d_maxd, &d_scale, &d_red, &d_lm, &d_osum, &d_camblk,
-                        &d_ptcnt, &d_plist, &d_pcnt, &d_skeys, &d_svals, &d_kb, &d_chist, &d_kdst, &d_rblk, &d_sbits, &d_srank, &d_Z, &d_campart, &d_teth, &d_tout, &d_ptlist, &d_sentries, &d_spairs,
-                        &d_schunks, &d_spart, &d_sfinish, &d_epos, &d_chi_lin, &d_livebuf, &d_removed, &d_camflag,
-                        &d_ikeys, &d_ivals, &d_isum, &d_iacc, &d_ctab, &d_csort_tmp})
-            if (idle)
-                b->retire();  // the stream is synchronised: the blocks are idle (common.hpp block cache)
-            else
-                b->release();
-        if (idle) {
-            h_olist.retire();
-            h_state.retire();
-            h_kb.retire();
-            h_isum.retire();
-            h_stage.retire();
-            h_dma.retire();
-        } else {
-            h_olist.release();
-            h_state.release();
-            h_kb.release();
-            h_isum.release();
-            h_stage.release();
-            h_dma.release();
-        }
+        for (BufferNode* b = bufs; b; b = b->next) b->drop(b, idle);
         iacc_clean = false;
         stage_off = dma_off = 0;
         pending.k = 0;
@@ -2763,14 +2842,6 @@ struct BundleAdjuster {
                 (void)hipStreamDestroy(st);
         }
         st = nullptr;
-        if (h_ctl) {
-            if (idle && ctl_bytes)
-                mage::pool_retire(2, h_ctl, ctl_bytes);
-            else
-                (void)hipHostFree(h_ctl);
-        }
-        h_ctl = nullptr;
-        ctl_bytes = 0;
     }
 
     // Host-to-device copies are staged in pinned memory.  Large ones are DMA copies from a pinned
@@ -2779,8 +2850,8 @@ struct BundleAdjuster {
     // of one copy call each.  A ring / the arena restarts from its beginning only after a stream
     // synchronisation, so no pending copy sees its source change; it grows only when a single copy
     // does not fit it.
-    MappedBuffer h_stage;  // small copies (read by gather_copy over the fabric)
-    PinnedBuffer h_dma;    // large copies (DMA source)
+    Listed<MappedBuffer> h_stage{bufs};  // small copies (read by gather_copy over the fabric)
+    Listed<PinnedBuffer> h_dma{bufs};    // large copies (DMA source)
     size_t stage_off = 0, dma_off = 0;
     GatherList pending{};
     static constexpr size_t GATHER_MAX_BYTES = 64 << 10;
@@ -2839,23 +2910,24 @@ struct BundleAdjuster {
         return MAGE_OK;
     }
     template <typename T>
-    mage_status upload(DeviceBuffer& b, const std::vector<T>& v)
+    mage_status upload(DeviceArray<T>& b, const std::vector<T>& v)
     {
         return upload(b, v.data(), v.size());
     }
     template <typename T>
-    mage_status upload(DeviceBuffer& b, const T* v, size_t n)
+    mage_status upload(DeviceArray<T>& b, const T* v, size_t n)
     {
+        const size_t bytes = std::max<size_t>(n * sizeof(T), 16);
         // a growing buffer is freed by reserve(): launch the queued copies into it first
-        if (b.ptr && std::max<size_t>(n * sizeof(T), 16) > b.bytes && pending_overlaps(b.ptr, b.bytes)) flush_uploads();
-        mage_status r = b.reserve(std::max<size_t>(n * sizeof(T), 16));
+        if (b.ptr && bytes > b.bytes && pending_overlaps(b.ptr, b.bytes)) flush_uploads();
+        mage_status r = b.DeviceBuffer::reserve(bytes);
         if (r != MAGE_OK) return r;
         return stage_copy(b.ptr, v, n * sizeof(T));
     }
 
     // export_state's GetPose / GetPoint outputs of the current estimate (valid while export_seq is
     // the last sequence number launched and export_cur the current buffer)
-    MappedBuffer h_state;
+    Listed<MappedBuffer> h_state{bufs};
     unsigned export_seq = 0;
     int export_cur = -1;
     bool export_wanted = false;  // the caller read the state since the last step
@@ -2866,7 +2938,7 @@ struct BundleAdjuster {
             return;
         }
         launch("ba.export_state", export_state, dim3(1), dim3(1024), 0, st, state(cur), C, P, h_state.device<float>(),
-               seq_dev(), ++seq_counter);
+               d_ctl(), ++seq_counter);
         export_seq = seq_counter;
         export_cur = cur;
     }
@@ -2904,12 +2976,11 @@ struct BundleAdjuster {
         auto pass = [&](const KeyT* ki, const ValT* vi, KeyT* ko, ValT* vo, int ndig, int dbits, int shift,
                         unsigned dmask) -> mage_status {
             mage_status rr;
-            if ((rr = d_chist.reserve((size_t)nblk * ndig * sizeof(int))) != MAGE_OK) return rr;
-            launch("ba.sort_count", csort_count<KeyT>, dim3(nblk), dim3(CS_BLOCK), 0, st, n, ndig, ki, d_chist.as<int>(),
-                   shift, dmask);
-            launch("ba.sort_scan", csort_scan, dim3(1), dim3(1024), 0, st, nblk, ndig, d_chist.as<int>());
+            if ((rr = d_chist.reserve((size_t)nblk * ndig)) != MAGE_OK) return rr;
+            launch("ba.sort_count", csort_count<KeyT>, dim3(nblk), dim3(CS_BLOCK), 0, st, n, ndig, ki, d_chist, shift, dmask);
+            launch("ba.sort_scan", csort_scan, dim3(1), dim3(1024), 0, st, nblk, ndig, d_chist);
             launch("ba.sort_scatter", csort_scatter<KeyT, ValT>, dim3(nblk), dim3(CS_BLOCK), 0, st, n, ndig, dbits, ki, vi,
-                   (const int*)d_chist.as<int>(), ko, vo, shift, dmask);
+                   d_chist, ko, vo, shift, dmask);
             return MAGE_OK;
         };
         if (nkeys <= CS_MAX_KEYS) return pass(kin, vin, kout, vout, nkeys, kbits, 0, ~0u);
@@ -2917,15 +2988,9 @@ struct BundleAdjuster {
         // two (keys, values) copies, each array starting 128-byte aligned
         const size_t kb = ((size_t)n * sizeof(KeyT) + 127) / 128 * 128, vb = ((size_t)n * sizeof(ValT) + 127) / 128 * 128;
         if ((r = d_csort_tmp.reserve(2 * (kb + vb))) != MAGE_OK) return r;
-        KeyT* tk[2] = {d_csort_tmp.as<KeyT>(), nullptr};
-        ValT* tv[2] = {nullptr, nullptr};
-        {
-            char* base = d_csort_tmp.as<char>();
-            tk[0] = reinterpret_cast<KeyT*>(base);
-            tv[0] = reinterpret_cast<ValT*>(base + kb);
-            tk[1] = reinterpret_cast<KeyT*>(base + kb + vb);
-            tv[1] = reinterpret_cast<ValT*>(base + 2 * kb + vb);
-        }
+        char* base = d_csort_tmp;  // the scratch copies' storage, typed here
+        KeyT* tk[2] = {reinterpret_cast<KeyT*>(base), reinterpret_cast<KeyT*>(base + kb + vb)};
+        ValT* tv[2] = {reinterpret_cast<ValT*>(base + kb), reinterpret_cast<ValT*>(base + 2 * kb + vb)};
         const KeyT* ki = kin;
         const ValT* vi = vin;
         for (int ps = 0; ps < npass; ps++) {
@@ -2953,16 +3018,15 @@ struct BundleAdjuster {
     {
         mage_status r;
         const int Pm = std::max(P, 1), nk = nb * nb;
-        if ((r = d_plist.reserve((size_t)std::max(ncsr, 1) * sizeof(int2))) != MAGE_OK) return r;
-        if ((r = d_pcnt.reserve((size_t)3 * Pm * sizeof(int))) != MAGE_OK) return r;
-        int* pcnt = d_pcnt.as<int>();
+        if ((r = d_plist.reserve((size_t)std::max(ncsr, 1))) != MAGE_OK) return r;
+        if ((r = d_pcnt.reserve((size_t)3 * Pm)) != MAGE_OK) return r;
+        int* pcnt = d_pcnt;
         int* poff = pcnt + Pm;
         int* klen = pcnt + 2 * Pm;
         const unsigned gp = (unsigned)((P + 255) / 256);
-        launch("ba.schur_lists", schur_point_lists, dim3(gp), dim3(256), 0, st, P, (const int*)d_pstart.as<int>(),
-               (const int*)d_pedges.as<int>(), (const int*)d_ecam.as<int>(), (const int*)d_camh.as<int>(),
-               (const int*)d_epos.as<int>(), (const int*)d_ptfree.as<int>(), d_plist.as<int2>(), pcnt, klen);
-        launch("ba.schur_scan", scan_exclusive, dim3(1), dim3(1024), 0, st, P, (const int*)pcnt, poff);
+        launch("ba.schur_lists", schur_point_lists, dim3(gp), dim3(256), 0, st, P, d_pstart, d_pedges, d_ecam, d_camh,
+               d_epos, d_ptfree, d_plist, pcnt, klen);
+        launch("ba.schur_scan", scan_exclusive, dim3(1), dim3(1024), 0, st, P, pcnt, poff);
         if ((r = h_kb.reserve((size_t)std::max(2 * nk, 2) * sizeof(int))) != MAGE_OK) return r;
         MAGE_HIP(hipMemcpyAsync(h_kb.ptr, poff + P - 1, sizeof(int), hipMemcpyDeviceToHost, st));
         MAGE_HIP(hipMemcpyAsync(h_kb.as<int>() + 1, pcnt + P - 1, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -2972,20 +3036,19 @@ struct BundleAdjuster {
         MAGE_REQUIRE(nmax < (1ll << 31), MAGE_EUNSUPPORTED, "Schur product list exceeds 2^31 entries");
         if (nmax == 0) return MAGE_OK;
         const size_t pad = nprod_pad(nmax);
-        if ((r = d_skeys.reserve(2 * pad * sizeof(uint16_t))) != MAGE_OK) return r;
-        if ((r = d_svals.reserve(2 * pad * sizeof(unsigned long long))) != MAGE_OK) return r;
-        if ((r = d_kb.reserve((size_t)2 * nk * sizeof(int))) != MAGE_OK) return r;
-        uint16_t* kin = d_skeys.as<uint16_t>();
+        if ((r = d_skeys.reserve(2 * pad)) != MAGE_OK) return r;
+        if ((r = d_svals.reserve(2 * pad)) != MAGE_OK) return r;
+        if ((r = d_kb.reserve((size_t)2 * nk)) != MAGE_OK) return r;
+        uint16_t* kin = d_skeys;
         uint16_t* kout = kin + pad;
-        unsigned long long* vin = d_svals.as<unsigned long long>();
+        unsigned long long* vin = d_svals;
         unsigned long long* vout = vin + pad;
         MAGE_HIP(hipMemsetAsync(d_kb.ptr, 0, (size_t)2 * nk * sizeof(int), st));
-        launch("ba.schur_products", schur_point_products, dim3(gp), dim3(256), 0, st, P, nb,
-               (const int*)d_pstart.as<int>(), (const int2*)d_plist.as<int2>(), (const int*)poff, (const int*)klen, kin, vin);
+        launch("ba.schur_products", schur_point_products, dim3(gp), dim3(256), 0, st, P, nb, d_pstart, d_plist, poff, klen,
+               kin, vin);
         if ((r = stable_key_sort(kin, vin, kout, vout, (int)nmax, nk)) != MAGE_OK) return r;
         const unsigned gn = (unsigned)((nmax + 255) / 256);
-        launch("ba.schur_bounds", schur_list_bounds, dim3(gn), dim3(256), 0, st, (const uint16_t*)kout, (int)nmax, nk,
-               d_kb.as<int>());
+        launch("ba.schur_bounds", schur_list_bounds, dim3(gn), dim3(256), 0, st, kout, (int)nmax, nk, d_kb);
         MAGE_HIP(hipGetLastError());
         MAGE_HIP(hipMemcpyAsync(h_kb.ptr, d_kb.ptr, (size_t)2 * nk * sizeof(int), hipMemcpyDeviceToHost, st));
         MAGE_HIP(hipStreamSynchronize(st));
@@ -3056,77 +3119,62 @@ struct BundleAdjuster {
             if ((r = upload(d_camflag, camflag)) != MAGE_OK) return r;
             flush_uploads();
         }
-        for (auto pr : {std::make_pair(&d_camh, (size_t)Cm * 4), std::make_pair(&d_camblk, (size_t)Cm * 4),
-                        std::make_pair(&d_ptfree, (size_t)Pm * 4), std::make_pair(&d_ptcnt, (size_t)Pm * 4),
-                        std::make_pair(&d_pstart, (size_t)(Pm + 1) * 4), std::make_pair(&d_cstart, (size_t)(Cm + 1) * 4),
-                        std::make_pair(&d_pedges, (size_t)Em * 4), std::make_pair(&d_cedges, (size_t)Em * 4),
-                        std::make_pair(&d_cpt, (size_t)Em * 4), std::make_pair(&d_epos, (size_t)Em * 4),
-                        std::make_pair(&d_pe, (size_t)Em * 16),
-                        std::make_pair(&d_active, (size_t)Em), std::make_pair(&d_ikeys, (size_t)Em * 8),
-                        std::make_pair(&d_ivals, (size_t)Em * 4), std::make_pair(&d_isum, nsum * 4)})
-            if ((r = pr.first->reserve(pr.second)) != MAGE_OK) return r;
+        if ((r = reserve_all(d_camh, Cm, d_camblk, Cm, d_ptfree, Pm, d_ptcnt, Pm, d_pstart, Pm + 1, d_cstart, Cm + 1,
+                             d_pedges, Em, d_cedges, Em, d_cpt, Em, d_epos, Em, d_pe, Em, d_active, Em,
+                             d_ikeys, 2 * Em, d_ivals, Em, d_isum, nsum)) != MAGE_OK)
+            return r;
         if ((r = h_isum.reserve(nsum * 4)) != MAGE_OK) return r;
-        int* sum = d_isum.as<int>();
+        int* sum = d_isum;
         int* s_ccnt = sum + INIT_HDR;
         int* s_camblk = s_ccnt + C;
         int* s_rc = s_camblk + C;
         int* s_kcnt = s_rc + nbm;
-        unsigned* k0 = d_ikeys.as<unsigned>();
+        unsigned* k0 = d_ikeys;
         unsigned* k1 = k0 + Em;
-        int* v0 = d_ivals.as<int>();
+        int* v0 = d_ivals;
         // accumulators kept zero between initialisations (cleared by their consumers): per point,
         // per camera, per-point fill cursors; cleared here only when (re)allocated or after a
         // chain that did not complete
-        const size_t acc_bytes = (2 * Pm + Cm) * 4;
-        if (d_iacc.bytes < acc_bytes || !iacc_clean) {
-            if ((r = d_iacc.reserve(acc_bytes)) != MAGE_OK) return r;
+        const size_t nacc = 2 * Pm + Cm;
+        if (d_iacc.bytes < nacc * 4 || !iacc_clean) {
+            if ((r = d_iacc.reserve(nacc)) != MAGE_OK) return r;
             MAGE_HIP(hipMemsetAsync(d_iacc.ptr, 0, d_iacc.bytes, st));
         }
         iacc_clean = false;
-        int* pacc = d_iacc.as<int>();
+        int* pacc = d_iacc;
         int* cacc = pacc + Pm;
         int* pcur = cacc + Cm;
         const unsigned ge = (unsigned)((E + 255) / 256);
         if (E > 0)
             launch("ba.init_edges", init_edges, dim3(ge), dim3(256), C <= INIT_LDS_CAMS ? C * 4 : 0, st, E, C,
-                   points_fixed ? 1 : 0, (const int*)d_ecam.as<int>(), (const int*)d_ept.as<int>(),
-                   (const unsigned char*)d_removed.as<unsigned char>(), (const unsigned char*)d_camflag.as<unsigned char>(),
-                   d_active.as<unsigned char>(), pacc, cacc, d_epos.as<int>(), k0);
-        launch("ba.init_scan", init_scan, dim3(1), dim3(1024), 0, st, C, P, nbm, points_fixed ? 1 : 0,
-               (const unsigned char*)d_camflag.as<unsigned char>(), pacc, cacc, d_ptcnt.as<int>(), d_pstart.as<int>(),
-               d_ptfree.as<int>(), d_cstart.as<int>(), d_camh.as<int>(), d_camblk.as<int>(), sum);
+                   points_fixed ? 1 : 0, d_ecam, d_ept, d_removed, d_camflag, d_active, pacc, cacc, d_epos, k0);
+        launch("ba.init_scan", init_scan, dim3(1), dim3(1024), 0, st, C, P, nbm, points_fixed ? 1 : 0, d_camflag, pacc,
+               cacc, d_ptcnt, d_pstart, d_ptfree, d_cstart, d_camh, d_camblk, sum);
         if (E > 0) {
             // point CSR in edge order (slots by atomics, each run sorted); camera CSR: that order
             // stably sorted by camera
-            launch("ba.init_pfill", init_pfill, dim3(ge), dim3(256), 0, st, E, (const int*)d_ept.as<int>(),
-                   (const unsigned char*)d_active.as<unsigned char>(), (const int*)d_pstart.as<int>(), pcur,
-                   d_pedges.as<int>());
+            launch("ba.init_pfill", init_pfill, dim3(ge), dim3(256), 0, st, E, d_ept, d_active, d_pstart, pcur, d_pedges);
             if (P > 0)
                 launch("ba.init_psort", init_psort, dim3((unsigned)((P + PSORT_WAVES - 1) / PSORT_WAVES)),
-                       dim3(PSORT_WAVES * kWave), 0, st, P, (const int*)d_pstart.as<int>(), (const int*)d_ecam.as<int>(),
-                       pcur, d_pedges.as<int>(), k0);
-            if ((r = stable_key_sort((const unsigned*)k0, (const int*)d_pedges.as<int>(), k1, v0, E, C + 1)) != MAGE_OK)
-                return r;
-            launch("ba.init_camcsr", init_camcsr, dim3(ge), dim3(256), 0, st, E, C, nbm, (const unsigned*)k1, (const int*)v0,
-                   (const int*)d_ept.as<int>(), (const int*)d_camh.as<int>(), (const int*)d_ptfree.as<int>(),
-                   d_cedges.as<int>(), d_cpt.as<int>(), d_epos.as<int>(), sum, s_rc);
-            launch("ba.init_pcache", init_pcache, dim3(ge), dim3(256), 0, st, E, P, (const int*)d_pstart.as<int>(),
-                   (const int*)d_pedges.as<int>(), (const int*)d_ecam.as<int>(), (const int*)d_camh.as<int>(),
-                   (const int*)d_epos.as<int>(), d_pe.as<int4>());
+                       dim3(PSORT_WAVES * kWave), 0, st, P, d_pstart, d_ecam, pcur, d_pedges, k0);
+            if ((r = stable_key_sort<unsigned, int>(k0, d_pedges, k1, v0, E, C + 1)) != MAGE_OK) return r;
+            launch("ba.init_camcsr", init_camcsr, dim3(ge), dim3(256), 0, st, E, C, nbm, k1, v0, d_ept, d_camh, d_ptfree,
+                   d_cedges, d_cpt, d_epos, sum, s_rc);
+            launch("ba.init_pcache", init_pcache, dim3(ge), dim3(256), 0, st, E, P, d_pstart, d_pedges, d_ecam, d_camh,
+                   d_epos, d_pe);
         }
         const bool bitmap_fits = PW <= SC_LDS_WORDS && nbm > 0 && P > 0;
         if (bitmap_fits) {
-            if ((r = d_sbits.reserve(((size_t)nbm + 1) * PW * 4)) != MAGE_OK) return r;
-            if ((r = d_srank.reserve((size_t)nbm * PW * 4)) != MAGE_OK) return r;
-            uint32_t* A = d_sbits.as<uint32_t>();
-            launch("ba.schur_bitmaps", sc_bitmaps, dim3(nbm + 1), dim3(1024), 0, st, P, (const int*)sum,
-                   (const int*)d_camblk.as<int>(), (const int*)d_cstart.as<int>(), (const int*)d_cpt.as<int>(),
-                   (const int*)d_ptfree.as<int>(), A, d_srank.as<int>(), A + (size_t)nbm * PW);
-            launch("ba.schur_counts", sc_pair_counts, dim3(nbm, nbm), dim3(64), 0, st, (const int*)sum, PW,
-                   (const uint32_t*)A, (const uint32_t*)(A + (size_t)nbm * PW), s_kcnt);
+            if ((r = d_sbits.reserve(((size_t)nbm + 1) * PW)) != MAGE_OK) return r;
+            if ((r = d_srank.reserve((size_t)nbm * PW)) != MAGE_OK) return r;
+            uint32_t* A = d_sbits;
+            launch("ba.schur_bitmaps", sc_bitmaps, dim3(nbm + 1), dim3(1024), 0, st, P, sum, d_camblk, d_cstart, d_cpt,
+                   d_ptfree, A, d_srank, A + (size_t)nbm * PW);
+            launch("ba.schur_counts", sc_pair_counts, dim3(nbm, nbm), dim3(64), 0, st, sum, PW, A, A + (size_t)nbm * PW,
+                   s_kcnt);
         }
-        launch("ba.init_summary", summary_out, dim3(1), dim3(1024), 0, st, (const int*)sum, (int)nsum, h_isum.device<int>(),
-               seq_dev(), ++seq_counter);
+        launch("ba.init_summary", summary_out, dim3(1), dim3(1024), 0, st, sum, (int)nsum, h_isum.device<int>(), d_ctl(),
+               ++seq_counter);
         MAGE_HIP(hipGetLastError());
         if ((r = wait_seq(seq_counter)) != MAGE_OK) return r;
         iacc_clean = true;
@@ -3152,29 +3200,23 @@ struct BundleAdjuster {
             if ((r = upload(d_q[0], q)) != MAGE_OK) return r;
             if ((r = upload(d_t[0], t)) != MAGE_OK) return r;
             if ((r = upload(d_p[0], p)) != MAGE_OK) return r;
-            if ((r = d_q[1].reserve(d_q[0].bytes)) != MAGE_OK) return r;
-            if ((r = d_t[1].reserve(d_t[0].bytes)) != MAGE_OK) return r;
-            if ((r = d_p[1].reserve(d_p[0].bytes)) != MAGE_OK) return r;
+            if ((r = d_q[1].DeviceBuffer::reserve(d_q[0].bytes)) != MAGE_OK) return r;
+            if ((r = d_t[1].DeviceBuffer::reserve(d_t[0].bytes)) != MAGE_OK) return r;
+            if ((r = d_p[1].DeviceBuffer::reserve(d_p[0].bytes)) != MAGE_OK) return r;
             cur = 0;
             state_on_device = true;
         }
         flush_uploads();
         {
             const size_t npm = std::max(np, 16);
-            for (auto pr : {std::make_pair(&d_err, Em * 2 * 8), std::make_pair(&d_Hll, Pm * 9 * 8),
-                            std::make_pair(&d_bl, Pm * 3 * 8), std::make_pair(&d_Hpl, (size_t)std::max(n_entries, 1) * EQ_N * 8),
-                            std::make_pair(&d_Hpp, Cm * 36 * 8), std::make_pair(&d_bp, Cm * 6 * 8),
-                            std::make_pair(&d_Z, (size_t)std::max(n_entries, 1) * EG_N * 8),
-                            std::make_pair(&d_campart, Cm * CAM_CHUNKS * 27 * 8),
-                            std::make_pair(&d_S, npm * npm * 8), std::make_pair(&d_rhs, npm * 8),
-                            std::make_pair(&d_x, (npm + 3 * Pm + 1) * 8), std::make_pair(&d_chi, (Pm + teth.size()) * 8),
-                            std::make_pair(&d_chi_lin, (Pm + teth.size()) * 8),
-                            std::make_pair(&d_tout, std::max<size_t>(teth.size(), 1) * TETHER_OUT * 8),
-                            std::make_pair(&d_maxd, (Pm + Cm) * 8), std::make_pair(&d_scale, (Pm + Cm) * 8),
-                            std::make_pair(&d_red, (size_t)CTL_DOUBLES * 8), std::make_pair(&d_lm, sizeof(LmDev)),
-                            std::make_pair(&d_osum, ((size_t)std::max<int>((int)(Em / BA_THREADS), group_grid((int)Pm)) + 2) * 4 * 8)})
-                if ((r = pr.first->reserve(pr.second)) != MAGE_OK) return r;
-            if ((r = d_livebuf.reserve(sizeof(LiveCtl))) != MAGE_OK) return r;
+            const size_t nrec = std::max(n_entries, 1), nchi = Pm + teth.size();
+            const size_t nosum = ((size_t)std::max<int>((int)(Em / BA_THREADS), group_grid((int)Pm)) + 2) * 4;
+            if ((r = reserve_all(d_err, Em * 2, d_Hll, Pm * 9, d_bl, Pm * 3, d_Hpl, nrec * EQ_N, d_Hpp, Cm * 36, d_bp, Cm * 6,
+                                 d_Z, nrec * EG_N, d_campart, Cm * CAM_CHUNKS * 27, d_S, npm * npm, d_rhs, npm,
+                                 d_x, npm + 3 * Pm + 1, d_chi, nchi, d_chi_lin, nchi,
+                                 d_tout, std::max<size_t>(teth.size(), 1) * TETHER_OUT, d_maxd, Pm + Cm, d_scale, Pm + Cm,
+                                 d_lm, 1, d_osum, nosum, d_live, 1)) != MAGE_OK)
+                return r;
             if ((r = h_olist.reserve(Em * 2 * 4 + 16)) != MAGE_OK) return r;
             // one launch clears: the live counters, the max-diagonal / scale partials, S (chol_tiles
             // reads S without writing it and every trial rewrites the same covisible pair blocks, so
@@ -3186,7 +3228,7 @@ struct BundleAdjuster {
                 cl.n[cl.k++] = (unsigned)(bytes / 4);
             };
             static_assert(sizeof(LiveCtl) % 4 == 0, "LiveCtl is cleared as words");
-            add(d_livebuf.ptr, sizeof(LiveCtl));
+            add(d_live.ptr, sizeof(LiveCtl));
             add(d_maxd.ptr, (Pm + Cm) * 8);
             add(d_scale.ptr, (Pm + Cm) * 8);
             add(d_S.ptr, npm * npm * 8);
@@ -3201,18 +3243,10 @@ struct BundleAdjuster {
         }
         iteration = 0;
         dirty = false;
-        eager = false;
-        if (!useless && teth.empty()) {
-            // the first call's linearisation (the one lm_solve would launch: same huber width,
-            // lambda from the user or computeLambdaInit's reduction), taken up by lm_solve
-            const bool init = user_lambda <= 0;
-            if ((r = linearize(init ? std::numeric_limits<double>::quiet_NaN() : user_lambda, init)) != MAGE_OK) return r;
-            eager = true;
-            eager_init = init;
-            eager_huber = huber;
-            eager_lambda = init ? 0.0 : user_lambda;
-            eager_cur = cur;
-        }
+        queued.invalidate();
+        // the first call's linearisation (the one lm_solve would launch: same huber width,
+        // lambda from the user or computeLambdaInit's reduction), taken up by lm_solve
+        if (!useless && teth.empty() && (r = linearize(user_lambda <= 0, user_lambda, true)) != MAGE_OK) return r;
         pt.mark("state + buffers + linearisation");
         const bool bitmaps = !dup && bitmap_fits && nb > 0 && nfp > 0;
         // covisible camera pairs (h1 <= h2) of the reduced system: every pair sharing a free point
@@ -3294,27 +3328,23 @@ struct BundleAdjuster {
                 rblk[h] = (int)(pbeg[pi] + pcount[pi]);
             }
             // + the padding entry after the last list (written by schur_rhs)
-            if ((r = d_sentries.reserve(((size_t)pbeg[npairs] + 1) * sizeof(int2))) != MAGE_OK) return r;
+            if ((r = d_sentries.reserve((size_t)pbeg[npairs] + 1)) != MAGE_OK) return r;
             if (bitmaps)  // sc_pair_fill: a pair's first product slot (-1: no products)
                 for (int k = 0; k < nk; k++) kdst[k] = kcount[k] > 0 ? kdst[k] + kstart[k] : -1;
             if ((r = upload(d_kdst, kdst)) != MAGE_OK) return r;
             if ((r = upload(d_rblk, rblk)) != MAGE_OK) return r;
             flush_uploads();
             if (bitmaps) {
-                uint32_t* A = d_sbits.as<uint32_t>();
-                launch("ba.schur_fill", sc_pair_fill, dim3(nb, nb), dim3(64), 0, st, nb, PW, (const uint32_t*)A,
-                       (const int*)d_srank.as<int>(), (const uint32_t*)(A + (size_t)nbm * PW), (const int*)d_camblk.as<int>(),
-                       (const int*)d_cstart.as<int>(), (const int*)d_kdst.as<int>(), d_sentries.as<int2>());
+                uint32_t* A = d_sbits;
+                launch("ba.schur_fill", sc_pair_fill, dim3(nb, nb), dim3(64), 0, st, nb, PW, A, d_srank,
+                       A + (size_t)nbm * PW, d_camblk, d_cstart, d_kdst, d_sentries);
             }
-            if (nprod_max > 0)
+            if (nprod_max > 0)  // the sorted halves of the key / value buffers (build_product_lists)
                 launch("ba.schur_scatter", schur_scatter, dim3((unsigned)((nprod_max + 255) / 256)), dim3(256), 0, st,
-                       (const uint16_t*)d_skeys.as<uint16_t>() + nprod_pad(nprod_max),
-                       (const unsigned long long*)d_svals.as<unsigned long long>() + nprod_pad(nprod_max),
-                       (int)nprod_max, (const int*)d_kdst.as<int>(), d_sentries.as<int2>());
+                       d_skeys + nprod_pad(nprod_max), d_svals + nprod_pad(nprod_max), (int)nprod_max, d_kdst, d_sentries);
             if (nb > 0)
-                launch("ba.schur_rhs", schur_rhs, dim3(nb), dim3(256), 0, st, (const int*)d_camblk.as<int>(),
-                       (const int*)d_cstart.as<int>(), (const int*)d_cpt.as<int>(), (const int*)d_ptfree.as<int>(),
-                       (const int*)d_rblk.as<int>(), d_sentries.as<int2>(), (int)pbeg[npairs]);
+                launch("ba.schur_rhs", schur_rhs, dim3(nb), dim3(256), 0, st, d_camblk, d_cstart, d_cpt, d_ptfree, d_rblk,
+                       d_sentries, (int)pbeg[npairs]);
             MAGE_HIP(hipGetLastError());
         }
         pt.mark("list scatter");
@@ -3407,51 +3437,80 @@ struct BundleAdjuster {
         if ((r = upload(d_teth, teth)) != MAGE_OK) return r;
         pt.mark("uploads");
         flush_uploads();
-        if ((r = d_spart.reserve((size_t)std::max(n_slots, 1) * 42 * 8)) != MAGE_OK) return r;
+        if ((r = d_spart.reserve((size_t)std::max(n_slots, 1) * 42)) != MAGE_OK) return r;
         pt.mark("buffers");
         return MAGE_OK;
     }
 
-    // Linearise the current state (errors, Hll/bl/Hpl, Hpp/bp) and reduce chi2 / max diagonal
-    // into d_red[0..2]; no host synchronisation.
-    // G (edge_schur's records) is valid for this lambda (NaN: not computed)
+    // The lambda edge_schur's records G (d_Z) are valid for (NaN: not computed).  A queued
+    // linearisation without `init` has computed G for its own lambda, so g_lambda == queued.lambda
+    // while it is valid.
     double g_lambda = std::numeric_limits<double>::quiet_NaN();
     int eval_blocks() const { return P > 0 ? group_grid(P) : 0; }
-    PointOut point_out(double* chi) const
-    {
-        return PointOut{d_err.as<double>(), d_Hll.as<double>(), d_bl.as<double>(), d_Hpl.as<double>(), d_Z.as<double>(),
-                        chi, d_maxd.as<double>()};
-    }
+    PointOut point_out(double* chi) const { return PointOut{d_err, d_Hll, d_bl, d_Hpl, d_Z, chi, d_maxd}; }
 
     // Linearise the current state (errors, Hll / bl / per-edge records, camera partials) in one
     // launch; with a known lambda (every iteration but the first) also G, so the first trial
-    // needs no edge_schur.  init_lambda: linearize_finish reduces chi2 / max diagonal
-    // (computeLambdaInit) for the host right away.  No host synchronisation.
-    mage_status linearize(double lam_for_g, bool init_lambda)
+    // needs no edge_schur.  init_lambda: lam is not known yet, linearize_finish reduces chi2 / max
+    // diagonal (computeLambdaInit) for the host right away.  queue: recorded in `queued` for the
+    // next lm_solve.  No host synchronisation.
+    mage_status linearize(bool init_lambda, double lam, bool queue)
     {
         Problem pb = problem();
         const int npb = eval_blocks(), ncb = nb_free * CAM_CHUNKS;
-        const bool with_g = std::isfinite(lam_for_g) && n_entries > 0 && !points_fixed;
-        if (npb + ncb > 0)
+        const bool with_g = !init_lambda && std::isfinite(lam) && n_entries > 0 && !points_fixed;
+        if (npb + ncb > 0)  // (nullptr: not speculative, no LmDev to read)
             launch("ba.linearize", linearize_kernel, dim3(npb + ncb), dim3(BA_THREADS), 0, st, pb, state(cur),
-                   point_out(d_chi_lin.as<double>()), with_g ? lam_for_g : 0.0, with_g ? 1 : 0, npb,
-                   (const int*)d_camblk.as<int>(), d_campart.as<double>(), state(1 - cur), (const LmDev*)nullptr);
-        g_lambda = with_g ? lam_for_g : std::numeric_limits<double>::quiet_NaN();
+                   point_out(d_chi_lin), with_g ? lam : 0.0, with_g ? 1 : 0, npb, d_camblk, d_campart, state(1 - cur), nullptr);
+        g_lambda = with_g ? lam : std::numeric_limits<double>::quiet_NaN();
         const int nt = (int)teth.size();
         if (nt > 0)
-            launch("ba.tether_eval", tether_eval, dim3((nt + 63) / 64), dim3(64), 0, st, (const Tether*)d_teth.as<Tether>(),
-                   nt, state(cur), 1, d_chi_lin.as<double>() + P, d_tout.as<double>());
+            launch("ba.tether_eval", tether_eval, dim3((nt + 63) / 64), dim3(64), 0, st, d_teth, nt, state(cur), 1,
+                   d_chi_lin + P, d_tout);
         if (init_lambda)
-            launch("ba.linearize_finish", linearize_finish, dim3(1), dim3(1024), 0, st, nb_free, (const int*)d_camblk.as<int>(),
-                   (const double*)d_campart.as<double>(), (const double*)d_chi_lin.as<double>(), P,
-                   (const double*)d_maxd.as<double>(), (const Tether*)d_teth.as<Tether>(), nt,
-                   (const double*)d_tout.as<double>(), d_Hpp.as<double>(), d_bp.as<double>(), h_ctl_dev);
+            launch("ba.linearize_finish", linearize_finish, dim3(1), dim3(1024), 0, st, nb_free, d_camblk, d_campart,
+                   d_chi_lin, P, d_maxd, d_teth, nt, d_tout, d_Hpp, d_bp, &d_ctl()->lin);
         MAGE_HIP(hipGetLastError());
+        if (queue) queued = QueuedLin{true, init_lambda, huber, lam, cur};
         return MAGE_OK;
     }
 
-    // One trial: solve with lambda, build the trial state in the other buffer, evaluate it.
-    // Reads back red[0..5] = {chi(current), -, -, chi(trial), scale, -} and the fail flag.
+    // reduce3's arguments.  The post-pass part (every launch): the block partials of ns states,
+    // the trial counters, the completion word; no sums.
+    ReduceArgs reduce_outliers(int ns, int oblocks)
+    {
+        ReduceArgs a{};
+        a.opart = d_osum;
+        a.oblocks = oblocks;
+        a.ns = ns;
+        a.ctl = d_ctl();
+        a.live = d_live;
+        a.seq = ++seq_counter;
+        return a;
+    }
+    // A trial's: + chi2 of the trial state, computeScale, chi2 of the linearised state, and with
+    // lmd the LM decision on the device.
+    ReduceArgs reduce_trial(int ns, int oblocks, LmDev* lmd, double lam, double cur_chi)
+    {
+        const int nt = (int)teth.size();
+        ReduceArgs a = reduce_outliers(ns, oblocks);
+        a.a = d_chi;
+        a.na = P + nt;
+        a.b = d_scale;
+        a.nb = P + C;
+        a.c = d_chi_lin;
+        a.nc = P + nt;
+        a.trial = 1;
+        a.lm = lmd;
+        a.lam = lam;
+        a.ni = ni;
+        a.cur = cur;
+        a.cur_chi = cur_chi;
+        return a;
+    }
+
+    // One trial: solve with lambda, build the trial state in the other buffer, evaluate it, and
+    // read the reduction back.
     // Speculative linearisation (MAGE_BA_SPEC_LIN, default on): queued behind each trial's reduce3,
     // on the state and lambda of the decision reduce3 takes on the device, so the next trial (after
     // a rejection) or the next call (after an acceptance) starts without the host round trip.
@@ -3459,75 +3518,67 @@ struct BundleAdjuster {
         const char* v = std::getenv("MAGE_BA_SPEC_LIN");
         return !(v && v[0] == '0');
     }();
-    bool spec_lin_queued = false;  // set by trial(): the host adopts the device's lambda
     bool last_call_removed = false;  // the previous StepBundleAdjustment removed outliers
-    mage_status trial(double lam, bool* ok, double red[6], bool speculate, double cur_chi = std::numeric_limits<double>::quiet_NaN())
+    struct TrialResult {
+        double chi2_cur, chi2_trial, scale;  // chi2_cur: of the linearised (current) state
+        bool solve_ok;                       // the Cholesky factorisation succeeded
+        bool spec_queued;                    // a speculative linearisation follows, for lam_dev:
+        double lam_dev;                      // the device's lambda for the next trial
+    };
+    mage_status trial(double lam, bool speculate, double cur_chi, TrialResult* res)
     {
         Problem pb = problem();
-        double* xp = d_x.as<double>();
         const int npb = eval_blocks();
         if (n_entries > 0 && !points_fixed && !(g_lambda == lam)) {
             launch("ba.edge_schur", edge_schur, dim3((n_entries + BA_THREADS - 1) / BA_THREADS), dim3(BA_THREADS), 0, st,
-                   pb, (const double*)d_Hll.as<double>(), (const double*)d_Hpl.as<double>(), lam, d_Z.as<double>());
+                   pb, d_Hll, d_Hpl, lam, d_Z);
             g_lambda = lam;
         }
         if (n > 0) {
             if (np > 16 * CT_MAXT) MAGE_HIP(hipMemsetAsync(d_S.ptr, 0, (size_t)np * np * 8, st));
-            launch("ba.schur_pairs", schur_chunks, dim3(n_sblocks), dim3(SC_THREADS), 0, st,
-                   (const SchurChunk*)d_schunks.as<SchurChunk>(), (const SchurPair*)d_spairs.as<SchurPair>(),
-                   (const int2*)d_sentries.as<int2>(), (const double*)d_Z.as<double>(), (const double*)d_Hpl.as<double>(),
-                   (const double*)d_camk.as<double>(), (const double*)d_bl.as<double>(), lam, np, n_entries,
-                   (const int*)d_ptlist.as<int>(), (const double*)d_tout.as<double>(), d_spart.as<double>(), d_S.as<double>(),
-                   d_rhs.as<double>());
-            const FinishArgs fin{(const int*)d_sfinish.as<int>(), n_sfinish, (const SchurPair*)d_spairs.as<SchurPair>(),
-                                 (const double*)d_spart.as<double>(), (const double*)d_campart.as<double>(),
-                                 (const Tether*)d_teth.as<Tether>(), (int)teth.size(), d_Hpp.as<double>(),
-                                 d_bp.as<double>(), lam, (const int*)d_ptlist.as<int>(), (const double*)d_tout.as<double>(),
-                                 d_S.as<double>(), d_rhs.as<double>()};
+            launch("ba.schur_pairs", schur_chunks, dim3(n_sblocks), dim3(SC_THREADS), 0, st, d_schunks, d_spairs,
+                   d_sentries, d_Z, d_Hpl, d_camk, d_bl, lam, np, n_entries, d_ptlist, d_tout, d_spart, d_S, d_rhs);
+            const FinishArgs fin{d_sfinish, n_sfinish, d_spairs, d_spart, d_campart, d_teth, (int)teth.size(),
+                                 d_Hpp, d_bp, lam, d_ptlist, d_tout, d_S, d_rhs};
             // (finishing these pairs inside chol_tiles' one workgroup instead measured 65 -> 138 us:
             // the ~14k entries' dependent partial loads serialise on one CU)
             if (n_sfinish > 0) launch("ba.schur_finish", schur_finish, dim3(n_sfinish), dim3(64), 0, st, fin, np);
             if (np <= 16 * CT_MAXT)
-                launch("ba.cholesky_solve", chol_tiles, dim3(1), dim3(CT_THREADS), 0, st,
-                       (const double*)d_S.as<double>(), np, n, (const double*)d_rhs.as<double>(), xp, d_failp(),
-                       (const uint16_t*)d_ctab.as<uint16_t>());
+                launch("ba.cholesky_solve", chol_tiles, dim3(1), dim3(CT_THREADS), 0, st, d_S, np, n, d_rhs, d_x, d_failp(),
+                       d_ctab);
             else
-                launch("ba.cholesky_solve", cholesky_solve, dim3(1), dim3(CH_THREADS), 0, st, d_S.as<double>(), np,
-                       n, (const double*)d_rhs.as<double>(), xp, d_failp());
+                launch("ba.cholesky_solve", cholesky_solve, dim3(1), dim3(CH_THREADS), 0, st, d_S, np, n, d_rhs, d_x,
+                       d_failp());
         }
         const int ncb = (C + BA_THREADS - 1) / BA_THREADS;
         // the trial state and its evaluation with the speculative post-pass (read back with this sync)
         const bool spec = speculate && E > 0;
-        SpecPass sp{state(cur), spec ? 1 : 0, outlier_max_err_sq, h_olist.device<uint32_t>(), E, d_osum.as<double>(), d_live()};
+        SpecPass sp{state(cur), spec ? 1 : 0, outlier_max_err_sq, h_olist.device<uint32_t>(), E, d_osum, d_live};
         if (npb + ncb > 0)
-            launch("ba.update_evaluate", update_evaluate, dim3(npb + ncb), dim3(BA_THREADS), 0, st, pb,
-                   (const double*)d_Z.as<double>(), (const double*)d_Hpl.as<double>(), (const double*)d_Hll.as<double>(),
-                   (const double*)d_bl.as<double>(), (const double*)xp, lam, state(cur), state(1 - cur),
-                   (const double*)d_bp.as<double>(), d_scale.as<double>(), npb, point_out(d_chi.as<double>()), sp);
+            launch("ba.update_evaluate", update_evaluate, dim3(npb + ncb), dim3(BA_THREADS), 0, st, pb, d_Z, d_Hpl, d_Hll,
+                   d_bl, d_x, lam, state(cur), state(1 - cur), d_bp, d_scale, npb, point_out(d_chi), sp);
         const int nt = (int)teth.size();
         if (nt > 0)
-            launch("ba.tether_eval", tether_eval, dim3((nt + 63) / 64), dim3(64), 0, st, (const Tether*)d_teth.as<Tether>(),
-                   nt, state(1 - cur), 0, d_chi.as<double>() + P, d_tout.as<double>());
+            launch("ba.tether_eval", tether_eval, dim3((nt + 63) / 64), dim3(64), 0, st, d_teth, nt, state(1 - cur), 0,
+                   d_chi + P, d_tout);
         // (not on a call's last step when the previous call removed outliers: a removal invalidates
         // the linearisation, and the reference's schedule removes some on most calls)
-        spec_lin_queued = spec_lin && !(speculate && last_call_removed) && nt == 0 && n > 0 && n_entries > 0 &&
-                          !points_fixed && npb + nb_free * CAM_CHUNKS > 0;
-        LmDev* lmd = spec_lin_queued ? d_lm.as<LmDev>() : nullptr;
-        launch("ba.reduce", reduce3, dim3(1), dim3(1024), 0, st, (const double*)d_chi.as<double>(), P + nt,
-               (const double*)d_scale.as<double>(), P + C, (const double*)d_maxd.as<double>(), 0, h_ctl_dev + 3,
-               (const double*)d_chi_lin.as<double>(), P + nt, h_ctl_dev + CTL_SCRATCH,
-               (const double*)d_osum.as<double>(), npb, spec ? 2 : 0, d_octl(), d_live(), seq_dev(), ++seq_counter,
-               lmd, lam, (double)ni, cur, cur_chi, h_ctl_dev + CTL_LMNEXT);
-        if (spec_lin_queued)
+        res->spec_queued = spec_lin && !(speculate && last_call_removed) && nt == 0 && n > 0 && n_entries > 0 &&
+                           !points_fixed && npb + nb_free * CAM_CHUNKS > 0;
+        LmDev* lmd = nullptr;
+        if (res->spec_queued) lmd = d_lm;
+        launch("ba.reduce", reduce3, dim3(1), dim3(1024), 0, st, reduce_trial(spec ? 2 : 0, npb, lmd, lam, cur_chi));
+        if (res->spec_queued)
             launch("ba.linearize", linearize_kernel, dim3(npb + nb_free * CAM_CHUNKS), dim3(BA_THREADS), 0, st, pb,
-                   state(0), point_out(d_chi_lin.as<double>()), 0.0, 1, npb, (const int*)d_camblk.as<int>(),
-                   d_campart.as<double>(), state(1), (const LmDev*)lmd);
+                   state(0), point_out(d_chi_lin), 0.0, 1, npb, d_camblk, d_campart, state(1), lmd);
         MAGE_HIP(hipGetLastError());
         mage_status r = wait_seq(seq_counter);
         if (r != MAGE_OK) return r;
-        for (int k = 0; k < 6; k++) red[k] = h_ctl[k];
-        red[0] = h_ctl[CTL_SCRATCH];  // chi2 of the linearised (current) state
-        *ok = ctl_fail() == 0;
+        res->chi2_cur = ctl().chi2_cur;
+        res->chi2_trial = ctl().trial.chi2;
+        res->scale = ctl().trial.scale;
+        res->solve_ok = ctl().outlier.fail == 0;
+        res->lam_dev = res->spec_queued ? ctl().lam_next : 0.0;
         return MAGE_OK;
     }
 
@@ -3539,42 +3590,34 @@ struct BundleAdjuster {
             lambda = user_lambda;
             ni = 2;
         }
-        const bool reuse = eager && eager_init == init_lambda && eager_huber == huber && eager_cur == cur &&
-                           (init_lambda || eager_lambda == lambda);
-        eager = false;
+        const bool reuse = queued.matches(init_lambda, huber, lambda, cur);
+        queued.invalidate();
         mage_status r = MAGE_OK;
-        if (!reuse && (r = linearize(init_lambda ? std::numeric_limits<double>::quiet_NaN() : lambda, init_lambda)) != MAGE_OK)
-            return r;
+        if (!reuse && (r = linearize(init_lambda, lambda, false)) != MAGE_OK) return r;
         double currentChi = 0;
         bool haveChi = false;
         if (init_lambda) {
             if ((r = read_ctl()) != MAGE_OK) return r;
-            currentChi = h_ctl[0];
+            currentChi = ctl().lin.chi2;
             haveChi = true;
-            lambda = 1e-5 * h_ctl[2];  // computeLambdaInit, tau = 1e-5
+            lambda = 1e-5 * ctl().lin.maxd;  // computeLambdaInit, tau = 1e-5
             ni = 2;
         }
         double rho = 0;
         int qmax = 0;
         do {
-            bool ok2 = true;
-            double red[6];
-            if ((r = trial(lambda, &ok2, red, speculate, haveChi ? currentChi : std::numeric_limits<double>::quiet_NaN())) !=
-                MAGE_OK)
+            TrialResult tr{};
+            if ((r = trial(lambda, speculate, haveChi ? currentChi : std::numeric_limits<double>::quiet_NaN(), &tr)) != MAGE_OK)
                 return r;
-            // the device's lambda for the next step when a speculative linearisation was queued (the
-            // same decision from the same doubles; its pow may differ from the host's in the last bit,
-            // and then the queued linearisation is not used)
-            const double lam_dev = spec_lin_queued ? h_ctl[CTL_LMNEXT] : 0.0;
             *spec_valid = speculate ? 1 : -1;  // rejected: the current state's result (list 1)
             if (!haveChi) {
-                currentChi = red[0];
+                currentChi = tr.chi2_cur;
                 haveChi = true;
             }
-            double tempChi = red[3];
-            if (!ok2) tempChi = std::numeric_limits<double>::max();
+            double tempChi = tr.chi2_trial;
+            if (!tr.solve_ok) tempChi = std::numeric_limits<double>::max();
             rho = currentChi - tempChi;
-            double scale = red[4] + 1e-3;
+            double scale = tr.scale + 1e-3;
             rho /= scale;
             stats.trials++;
             if (rho > 0 && std::isfinite(tempChi)) {
@@ -3592,22 +3635,20 @@ struct BundleAdjuster {
                 ni *= 2;
                 stats.rejected_trials++;  // pop: the current buffer is unchanged
             }
-            if (spec_lin_queued) {
-                if (lam_dev == lambda) {
-                    // the queued linearisation is of this state and lambda: the next trial's G (no
-                    // edge_schur) or the next call's eager linearisation
-                    eager = true;
-                    eager_init = false;
-                    eager_huber = huber;
-                    eager_lambda = lambda;
-                    eager_cur = cur;
+            // A speculative linearisation was queued for the device's lambda (the same decision
+            // from the same doubles; its pow may differ from the host's in the last bit)
+            if (tr.spec_queued) {
+                if (tr.lam_dev == lambda) {
+                    // it is of this state and lambda: the next trial's G (no edge_schur) or the
+                    // next call's eager linearisation
+                    queued = QueuedLin{true, false, huber, lambda, cur};
                     g_lambda = lambda;
                 } else {
                     // lambda differs in the last bit: the host's (g2o's) lambda holds; the queued
                     // linearisation's G is for the other value (its H and records are still this
                     // state's, so only G is redone, by edge_schur, for the next trial)
-                    eager = false;
-                    g_lambda = lam_dev;
+                    queued.invalidate();
+                    g_lambda = tr.lam_dev;
                 }
             }
             qmax++;
@@ -3641,9 +3682,8 @@ struct BundleAdjuster {
     void launch_outlier_pass(State s0, State s1, int ns)
     {
         const int ge = outlier_blocks();
-        launch("ba.outlier_pass", outlier_pass, dim3(ge), dim3(BA_THREADS), 0, st, problem(), s0, s1, ns, E,
-                           d_active.as<unsigned char>(), d_err.as<double>(), outlier_max_err_sq,
-                           h_olist.device<uint32_t>(), d_osum.as<double>(), d_live());
+        launch("ba.outlier_pass", outlier_pass, dim3(ge), dim3(BA_THREADS), 0, st, problem(), s0, s1, ns, E, d_active, d_err,
+               outlier_max_err_sq, h_olist.device<uint32_t>(), d_osum, d_live);
     }
 
     mage_status step(const float* hw, uint32_t nsteps, float maxErrSq, uint32_t* outliers, uint32_t cap,
@@ -3681,25 +3721,21 @@ struct BundleAdjuster {
         int k = spec_valid;
         if (k < 0) {
             launch_outlier_pass(state(cur), state(cur), 1);
-            // its block partials -> ctl->osum[0] (the chi2 outputs go to a scratch slot)
-            launch("ba.reduce", reduce3, dim3(1), dim3(1024), 0, st, (const double*)nullptr, 0, (const double*)nullptr, 0,
-                   (const double*)nullptr, 0, h_ctl_dev + CTL_SCRATCH, (const double*)nullptr, 0,
-                   h_ctl_dev + CTL_SCRATCH, (const double*)d_osum.as<double>(), outlier_blocks(), 1, d_octl(), d_live(),
-                   seq_dev(), ++seq_counter, (LmDev*)nullptr, 0.0, 0.0, 0, 0.0, (double*)nullptr);
+            // its block partials -> ctl().outlier.osum[0]
+            launch("ba.reduce", reduce3, dim3(1), dim3(1024), 0, st, reduce_outliers(1, outlier_blocks()));
             MAGE_HIP(hipGetLastError());
             if ((r = read_ctl()) != MAGE_OK) return r;
             k = 0;
         }
-        const double h[2] = {h_octl().osum[k][0], h_octl().osum[k][1]};
-        const uint32_t no = h_octl().count[k];
+        const double h[2] = {ctl().outlier.osum[k][0], ctl().outlier.osum[k][1]};
+        const uint32_t no = ctl().outlier.count[k];
         last_call_removed = no > 0;
         if (no > 0) {
             // the pass wrote the list into mapped host memory before the completion word
             const uint32_t* h_list = h_olist.host<uint32_t>() + (size_t)k * E;
             std::vector<uint32_t> list(h_list, h_list + no);
             launch("ba.drop_edges", drop_edges, dim3((no + BA_THREADS - 1) / BA_THREADS), dim3(BA_THREADS), 0, st,
-                   (const int*)d_ept.as<int>(), (const uint32_t*)(h_olist.device<uint32_t>() + (size_t)k * E), no,
-                   d_active.as<unsigned char>(), d_removed.as<unsigned char>(), d_ptcnt.as<int>(), d_ptfree.as<int>());
+                   d_ept, h_olist.device<uint32_t>() + (size_t)k * E, no, d_active, d_removed, d_ptcnt, d_ptfree);
             std::sort(list.begin(), list.end());  // g2o active-edge order = insertion order
             for (uint32_t k = 0; k < no; k++) {
                 camcnt[ecam[list[k]]]--;
@@ -3709,7 +3745,7 @@ struct BundleAdjuster {
             for (int c = 0; c < C; c++)
                 if (camh[c] >= 0 && camcnt[c] == 0 && cam_tethers[c] == 0) dirty = true;
             iteration = 0;  // removeEdge dirties the optimizer: next Step re-initialises (lambda init)
-            eager = false;  // a speculative linearisation ran before the removal
+            queued.invalidate();  // a speculative linearisation ran before the removal
         }
         *nOut = std::min(no, cap);
         *meanSq = (float)(h[0] / h[1]);
@@ -3726,18 +3762,10 @@ struct BundleAdjuster {
         // the reduction computeLambdaInit reads when no user lambda is set.
         const bool init_next = iteration == 0 && user_lambda <= 0;
         const double lam_next = iteration > 0 ? lambda : user_lambda;
-        const bool pending = eager && eager_init == init_next && eager_huber == huber && eager_cur == cur &&
-                             (init_next || eager_lambda == lam_next);  // (initialize() just launched it)
-        if (!dirty && !useless && !pending) {
-            const bool init = init_next;
-            const double lam = lam_next;
-            if ((r = linearize(init ? std::numeric_limits<double>::quiet_NaN() : lam, init)) != MAGE_OK) return r;
-            eager = true;
-            eager_init = init;
-            eager_huber = huber;
-            eager_lambda = init ? 0.0 : lam;
-            eager_cur = cur;
-        }
+        // (already queued: by the last trial's speculation, or initialize() just launched it)
+        if (!dirty && !useless && !queued.matches(init_next, huber, lam_next, cur) &&
+            (r = linearize(init_next, lam_next, true)) != MAGE_OK)
+            return r;
         spt.mark("step: export + eager");
         return no > cap ? MAGE_ECAPACITY : MAGE_OK;
     }
@@ -3760,21 +3788,15 @@ mage_status mage_ba_create(int32_t points_fixed, int device, mage_ba** out)
     b->points_fixed = points_fixed != 0;
     // a retired stream / control block of an earlier instance when there is one (MakeBundler
     // creates a BundlerLib per local-BA window; creation and hipHostFree cost ~0.1 ms each)
-    size_t ctl_bytes = 0;
     b->st = mage::stream_take();
-    b->h_ctl = static_cast<double*>(mage::pool_take(2, mage::BundleAdjuster::CTL_DOUBLES * sizeof(double), &ctl_bytes));
     if ((!b->st && hipStreamCreateWithFlags(&b->st, hipStreamNonBlocking) != hipSuccess) ||
-        (!b->h_ctl && (ctl_bytes = mage::BundleAdjuster::CTL_DOUBLES * sizeof(double),
-                       hipHostMalloc(reinterpret_cast<void**>(&b->h_ctl), ctl_bytes,
-                                     hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)) ||
-        (b->ctl_bytes = ctl_bytes, false) ||
-        hipHostGetDevicePointer(reinterpret_cast<void**>(&b->h_ctl_dev), b->h_ctl, 0) != hipSuccess ||
-        (std::memset(b->h_ctl, 0, mage::BundleAdjuster::CTL_DOUBLES * sizeof(double)), false)) {
+        b->ctl_buf.reserve(sizeof(mage::BaCtl)) != MAGE_OK) {
         b->release();
         delete b;
         mage::set_error("hipStreamCreate / hipHostMalloc failed");
         return MAGE_EDEVICE;
     }
+    std::memset(b->ctl_buf.ptr, 0, sizeof(mage::BaCtl));
     *out = b;
     return MAGE_OK;
 }
@@ -3900,7 +3922,7 @@ mage_status mage_ba_set_lambda(mage_ba* b, float lambda)
     MAGE_REQUIRE(b, MAGE_EINVAL, "null handle");
     b->iteration = 0;  // StepOptimizer::SetCurrentLambda (BundlerLib.cpp:123-130)
     b->user_lambda = (double)lambda;
-    b->eager = false;
+    b->queued.invalidate();
     return MAGE_OK;
 }
 
