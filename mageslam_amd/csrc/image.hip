@@ -11,7 +11,8 @@
 //                         in-range source taps
 //   remap_linear_kernel   per batch of frames: workgroup per 64x16 tile x 64 frames, thread per 4
 //                         output pixels.  The maps are read once as float4 (coalesced) and kept as
-//                         register coefficients: X = rint(u * 32) -> the short integer part and the
+//                         register coefficients: X = rint(u * 32) (INT_MIN when that is not an
+//                         int: a non-finite map entry is an outlier) -> the short integer part and the
 //                         5+5-bit fraction index of remap's fixed-point path, initInterTab2D's
 //                         bilinear weights (x 32768, the saturated (0,0) entry included).  Per frame
 //                         the tile's source box is staged in LDS with dword loads and the 4 taps of
@@ -92,10 +93,18 @@ struct RemapTap {
     int mode;  // 0: inlier 2x2 block, 1: outlier with some taps inside, 2: entirely outside
 };
 
+// cvRound as the x86 conversions (cvtss2si, _mm_cvtps_epi32) give it: round half to even, INT_MIN
+// for NaN, +-inf and anything outside [-2^31, 2^31).  __float2int_rn alone saturates and turns NaN
+// into 0, which would read a pixel near (0, 0) where remap writes the border value.
+__device__ __forceinline__ int remap_round(float v)
+{
+    return v >= -2147483648.0f && v < 2147483648.0f ? __float2int_rn(v) : INT_MIN;
+}
+
 __device__ __forceinline__ RemapTap remap_tap(int sw, int sh, float fu, float fv)
 {
     RemapTap t;
-    const int X = __float2int_rn(fu * 32.0f), Y = __float2int_rn(fv * 32.0f);
+    const int X = remap_round(fu * 32.0f), Y = remap_round(fv * 32.0f);
     t.sx = min(max(X >> 5, -32768), 32767);
     t.sy = min(max(Y >> 5, -32768), 32767);
     const int tx = X & 31, ty = Y & 31;

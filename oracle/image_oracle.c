@@ -16,6 +16,7 @@
  *     the 2x2 block, outliers read each in-range tap and 0 for the others, or 0 outright when the
  *     block is entirely outside.
  */
+#include <limits.h>
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
@@ -91,7 +92,13 @@ static void bilinear_weights(int a, int wts[4])
     }
 }
 
-static int iround_f(float v) { return (int)lrintf(v); }
+/* cvRound on x86 is cvtss2si / _mm_cvtps_epi32: round half to even, and the "integer indefinite"
+ * INT_MIN for NaN, +-inf and anything outside [-2^31, 2^31) (lrintf returns a long: the cast would wrap). */
+static int iround_f(float v)
+{
+    if (!(v >= -2147483648.0f && v < 2147483648.0f)) return INT_MIN;
+    return (int)lrintf(v);
+}
 
 void oracle_remap_linear(const uint8_t* src, int sw, int sh, int sstride, const float* mapx, const float* mapy, int dw,
                          int dh, uint8_t* dst, int dstride)
