@@ -247,6 +247,11 @@ struct RadiusFollow {
     uint32_t min_matches;
     double ratio;
 };
+// A pass with n matches of ns queries is weak: too few matches, or too small a share of the queries.
+__host__ __device__ inline bool radius_pass_weak(uint32_t n, uint32_t ns, uint32_t min_matches, double ratio)
+{
+    return n < min_matches || (double)n / (double)(ns > 1u ? ns : 1u) < ratio;
+}
 mage_status radius_match_indexed(const mage_keypoint* d_query_kp, const float* d_query_pos, const uint8_t* d_query_desc,
                                  int64_t query_pitch, const uint32_t* d_n_query, const mage_keypoint* d_target_kp,
                                  const uint8_t* d_target_desc, int64_t target_pitch, const uint32_t* d_n_target,

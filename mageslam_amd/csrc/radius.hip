@@ -68,7 +68,7 @@ __device__ __forceinline__ void radius_done(const RadiusParams& p, int pr, uint3
     const RadiusFollow& g = p.follow;
     if (!g.exec) return;
     const uint32_t ns = *g.ns;
-    const bool weak = n < g.min_matches || (double)n / (double)max(ns, 1u) < g.ratio;
+    const bool weak = radius_pass_weak(n, ns, g.min_matches, g.ratio);
     const uint32_t run = g.exec[g.k] && weak;
     g.exec[g.k + 1] = run;
     *g.nq_next = run ? ns : 0u;

@@ -2,210 +2,47 @@
 // (PoseEstimator::TryEstimatePoseFromKeyframe, PoseEstimator.cpp:439-607; TrackLocalMap's two
 // OptimizeCameraPose passes, TrackLocalMap.cpp:37-140; NewKeyFrameDecision.cpp:196) with every
 // per-frame decision taken on the device, so the host enqueues the whole sequence and
-// synchronises once.  Per frame, in one stream:
-//   trk_project     prediction (constant velocity on SE3, fp64) + ProjectUndistorted of the
-//                   keyframe's map points (f32), ordered compaction of the points in front
-//   radius x 3      RadiusMatch at SearchRadius / WiderSearchRadius (position overrides) /
-//                   ExtraWiderSearchRadius (keypoint positions); pass k+1 gets a zero query
-//                   count unless pass k ran and was weak (trk_weak), which the kernels skip
-//   trk_gather      the last pass's matches -> pose-BA observations, "lost" when too few
-//   pose BA 1       mage_ba_pose_batch_device (3 steps, Huber 4, 6^2)
-//   trk_filter      ordered compaction of pass 1's inliers
-//   pose BA 2       (4 steps, Huber 0.9, 4.5^2)
-//   trk_finish      the frame's pose / counts, keyframe decision, new keyframe's map points
-// Every expression matches track.cpp (same order, f32 projection, fp64 poses, no contraction:
-// the library is built with -ffp-contract=off), so the two loops give identical results.
+// synchronises once.  trk_init makes frame 0's keyframe; then per frame, in one stream:
+//   trk_project        prediction (constant velocity on SE3, fp64) + ProjectUndistorted of the
+//                      keyframe's map points (f32), ordered compaction of the points in front
+//                      (a launch of its own only for the first frame and after a local BA)
+//   radius x 3         RadiusMatch at SearchRadius / WiderSearchRadius (position overrides) /
+//                      ExtraWiderSearchRadius (keypoint positions); pass k+1 gets a zero query
+//                      count unless pass k ran and was weak (RadiusFollow, in pass k's kernel)
+//   trk_gather         the last pass's matches -> pose-BA observations, "lost" when too few
+//   pose BA 1          mage_ba_pose_batch_device (3 steps, Huber 4, 6^2)
+//   trk_filter[_lm]    ordered compaction of pass 1's inliers [+ the local map's candidate queries,
+//                      then the local-map search (localmap.hip) and trk_lm_assemble]
+//   pose BA 2          (4 steps, Huber 0.9, 4.5^2)
+//   trk_finish_project the frame's pose / counts, keyframe decision, new keyframe's map points,
+//                      then the next frame's trk_project part
+// Arithmetic: csrc/track_math.hpp, shared with track.cpp (identical results); buffers: track_bufs.hpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <cmath>
-#include <cstring>
 #include <vector>
 
 #include "common.hpp"
-#include "depth_noise.hpp"
 #include "ordered_take.hpp"
+#include "track_window.hpp"
 
 namespace mage {
 namespace {
 
+using namespace track;
+
 constexpr int TT = 1024;  // threads of the per-frame control kernels
-// RadiusMatch band-index ring of mage_track_sequence_device: chunks of BAND_CHUNK frames, two
-// chunks resident (the host runs at most a few frames ahead of the device)
-constexpr uint32_t BAND_CHUNK = 16, BAND_SLOTS = 2 * BAND_CHUNK;
-
-struct DPose {
-    double R[9];  // world -> camera, row-major
-    double t[3];
-};
-
-__device__ void d_mv(const double* R, const double* v, double* out)
-{
-    for (int i = 0; i < 3; i++) out[i] = (R[3 * i] * v[0] + R[3 * i + 1] * v[1]) + R[3 * i + 2] * v[2];
-}
-
-__device__ DPose d_inverse(const DPose& p)
-{
-    DPose q;
-    for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++) q.R[3 * r + c] = p.R[3 * c + r];
-    double m[3];
-    d_mv(q.R, p.t, m);
-    for (int i = 0; i < 3; i++) q.t[i] = -m[i];
-    return q;
-}
-
-__device__ DPose d_mul(const DPose& a, const DPose& b)
-{
-    DPose o;
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++)
-            o.R[3 * i + j] = (a.R[3 * i] * b.R[j] + a.R[3 * i + 1] * b.R[3 + j]) + a.R[3 * i + 2] * b.R[6 + j];
-    double m[3];
-    d_mv(a.R, b.t, m);
-    for (int i = 0; i < 3; i++) o.t[i] = m[i] + a.t[i];
-    return o;
-}
-
-__device__ DPose load_pose(const double* p)
-{
-    DPose q;
-    for (int i = 0; i < 9; i++) q.R[i] = p[i];
-    for (int i = 0; i < 3; i++) q.t[i] = p[9 + i];
-    return q;
-}
-
-__device__ void store_pose(double* p, const DPose& q)
-{
-    for (int i = 0; i < 9; i++) p[i] = q.R[i];
-    for (int i = 0; i < 3; i++) p[9 + i] = q.t[i];
-}
-
-constexpr int NKMAX = 8;  // keyframes of the local map
-
-struct Ctl {              // per-call control words (device)
-    uint32_t exec[3];     // radius pass k ran
-    uint32_t ns;          // queries (keyframe points in front of the predicted camera)
-    uint32_t lost;
-    uint32_t kf_first;    // keyframe ring: oldest slot, slots in use (ascending keyframe id)
-    uint32_t kf_count;
-    uint32_t kf_n[NKMAX]; // keyframe feature counts per slot
-    uint32_t lm_nq;       // local-map queries of the frame
-    uint32_t kf_id[NKMAX];  // frame index of the keyframe in each slot
-    uint32_t kf_an[NKMAX];  // associations per slot (the keyframe frame's pass-2 inliers)
-    uint32_t halt;        // local BA pending: every frame kernel is a no-op until the host clears it
-};
-
-struct TrackBufs {
-    Ctl* ctl;
-    double* pred;          // 12
-    // keyframe ring (NKMAX slots of cap entries; the reference keyframe is the newest slot)
-    mage_keypoint* kf_kp;
-    uint8_t* kf_desc;
-    float* kf_pts;
-    float* kf_mvd;   // mean viewing directions (3 per point)
-    float* kf_dmin;
-    float* kf_dmax;
-    double* kf_pose;      // 12 per slot (R row-major, t)
-    // mapping side (local BA): per point its refinement count and own-observation flag, per slot
-    // the associations (owner keyframe id, point index, keypoint x, y bits) and their flags
-    uint32_t* kf_ref;
-    uint8_t* kf_own;
-    int4* kf_assoc;
-    uint8_t* kf_aalive;
-    int2* src1;           // pose-BA observation sources (owner keyframe id, point index)
-    int2* src2;
-    float* info1;         // per observation: MapPointRefinementConfidence of the point
-    float* info2;
-    int2* lm_qsrc;
-    float* lm_qinfo;
-    uint32_t* prog;       // mapped host words {frame done, frame that requested a local BA}
-    // local-map search
-    uint32_t* lm_mask;    // unassociated keypoints (bit words)
-    uint8_t* lm_visited;  // reference-keyframe points associated as pass-1 inliers
-    int32_t* lm_hide;     // reference-keyframe points of pass-1 outliers: their keypoint
-    float* lm_qpos;
-    int32_t* lm_qoct;
-    int32_t* lm_qhide;
-    uint8_t* lm_qdesc;
-    float* lm_qpt;        // the queries' map point positions
-    int32_t* lm_res;
-    uint32_t* lm_status;
-    void* lm_scratch;
-    // queries
-    mage_keypoint* qkp;
-    uint8_t* qdesc;
-    float* qpos;
-    uint32_t* sel;
-    uint32_t* nq;          // 3: query count of each radius pass
-    mage_dmatch* m;        // 3 x cap
-    uint32_t* mn;          // 3
-    // pose BA
-    float* pos3;
-    float* r9;
-    float* intr4;
-    uint32_t* os1;         // 2
-    uint32_t* os2;         // 2
-    float* pts1;
-    float* uv1;
-    float* pts2;
-    float* uv2;
-    float* pos3_o1;
-    float* r9_o1;
-    float* pos3_o2;
-    float* r9_o2;
-    uint8_t* out1;
-    uint8_t* out2;
-    float* msq;
-};
-
-struct TrackConst {
-    float fx, fy, cx, cy;  // (float)K
-    double K[4];
-    double plane_z;
-    mage_track_settings s;
-    uint32_t cap;          // keypoints per frame slot
-    uint32_t nk;           // keyframe ring slots (max(local_map_keyframes, 1))
-    uint32_t qcap;         // local-map queries per frame (nk x cap)
-    uint32_t acap;         // associations per keyframe slot (cap + qcap)
-    float fmax[8], fmin[8];  // ComputeDMax / ComputeDMin factors per octave (powf on the host)
-    float log2s;           // log2(scale factor)
-};
-
-__device__ float dot3f(const float* a, const float* b) { return ((0.f + a[0] * b[0]) + a[1] * b[1]) + a[2] * b[2]; }
-
-// MapPointRefinementConfidence (Map/MappingMath.h:42-49): 1 - 1 / powf(1.5 + count, 2); the square
-// of 1.5 + count is exact in float, so x * x is powf's result
-__host__ __device__ inline float refinement_confidence(uint32_t count)
-{
-    const float x = 1.5f + (float)count;
-    return 1.f - 1.f / (x * x);
-}
-
-// Pose::GetWorldSpacePosition of the float view matrix (see track.cpp world_position)
-__device__ void world_position(const double* R, const double* t, float C[3])
-{
-    for (int i = 0; i < 3; i++) {
-        float s = 0.f;
-        for (int k = 0; k < 3; k++) s = s + (float)R[3 * k + i] * -(float)t[k];
-        C[i] = s + 0.f;
-    }
-}
 
 // Keyframe slot <- frame features (kp, desc, n) with map points back-projected at pose P onto the
-// plane and their MapPoint::UpdateMeanViewDirectionAndDistances attributes (track.cpp
-// map_point_attributes).
+// plane and their MapPoint::UpdateMeanViewDirectionAndDistances attributes.
 __device__ void make_keyframe(const TrackBufs& b, const TrackConst& c, uint32_t slot, const mage_keypoint* fk,
-                              const uint8_t* fd, uint32_t nf, const DPose& P, uint32_t fid)
+                              const uint8_t* fd, uint32_t nf, const Pose& P, uint32_t fid)
 {
-    const double fx = c.K[0], fy = c.K[1], cx = c.K[2], cy = c.K[3];
-    const double* R = P.R;
-    double C[3];
-    for (int j = 0; j < 3; j++) C[j] = -((R[j] * P.t[0] + R[3 + j] * P.t[1]) + R[6 + j] * P.t[2]);
-    float Cf[3];
-    world_position(P.R, P.t, Cf);
+    float R32[9], t32[3], Cf[3];
+    pose_f32(P.R, P.t, R32, t32);
+    world_position(R32, t32, Cf);
     const size_t o = (size_t)slot * c.cap;
     if (threadIdx.x < 12) b.kf_pose[12 * slot + threadIdx.x] = threadIdx.x < 9 ? P.R[threadIdx.x] : P.t[threadIdx.x - 9];
     for (uint32_t i = threadIdx.x; i < nf; i += TT) {
@@ -216,31 +53,13 @@ __device__ void make_keyframe(const TrackBufs& b, const TrackConst& c, uint32_t 
         uint4* d = reinterpret_cast<uint4*>(b.kf_desc + 32ull * (o + i));
         d[0] = s[0];
         d[1] = s[1];
-        const double u = ((double)fk[i].x - cx) / fx, v = ((double)fk[i].y - cy) / fy;
-        double dd[3];
-        for (int j = 0; j < 3; j++) dd[j] = (u * R[j] + v * R[3 + j]) + R[6 + j];
-        double lam = (c.plane_z - C[2]) / dd[2];
-        if (c.s.map_point_depth_noise != 0.f) lam = lam * depth_noise_factor(fid, i, c.s.map_point_depth_noise);
-        float Pp[3];
-        for (int j = 0; j < 3; j++) Pp[j] = (float)(C[j] + lam * dd[j]);
+        float Pp[3], mvd[3], dmin, dmax;
+        backproject_to_plane(fk[i].x, fk[i].y, P, c.K, c.plane_z, fid, i, c.s.map_point_depth_noise, Pp);
         for (int j = 0; j < 3; j++) b.kf_pts[3 * (o + i) + j] = Pp[j];
-        float vv[3] = {Pp[0] - Cf[0], Pp[1] - Cf[1], Pp[2] - Cf[2]};
-        const float d1 = sqrtf(dot3f(vv, vv));
-        if (d1 != 0) {
-            const float inv = 1.f / d1;
-            for (int j = 0; j < 3; j++) vv[j] = vv[j] * inv;
-        }
-        const float d2 = sqrtf(dot3f(vv, vv));
-        if (d2 != 0) {
-            const float inv = 1.f / d2;
-            for (int j = 0; j < 3; j++) vv[j] = vv[j] * inv;
-        }
-        for (int j = 0; j < 3; j++) b.kf_mvd[3 * (o + i) + j] = vv[j];
-        const float dl[3] = {Cf[0] - Pp[0], Cf[1] - Pp[1], Cf[2] - Pp[2]};
-        const float dist = sqrtf((dl[0] * dl[0] + dl[1] * dl[1]) + dl[2] * dl[2]);
-        const int oc = min(max(fk[i].octave, 0), 7);
-        b.kf_dmin[o + i] = dist * c.fmin[oc];
-        b.kf_dmax[o + i] = dist * c.fmax[oc];
+        point_attributes(Pp, Cf, fk[i].octave, c.fmin, c.fmax, mvd, dmin, dmax);
+        for (int j = 0; j < 3; j++) b.kf_mvd[3 * (o + i) + j] = mvd[j];
+        b.kf_dmin[o + i] = dmin;
+        b.kf_dmax[o + i] = dmax;
     }
 }
 
@@ -297,11 +116,10 @@ __device__ void project_frame(const TrackBufs& b, const TrackConst& c, int f, co
         return;
     }
     if (threadIdx.x == 0) {
-        const DPose p1 = load_pose(poses + 12ll * (f - 1));
-        const DPose pred = f < 2 ? p1 : d_mul(d_mul(p1, d_inverse(load_pose(poses + 12ll * (f - 2)))), p1);
+        const Pose p1 = load_pose(poses + 12ll * (f - 1));
+        const Pose pred = f < 2 ? p1 : predict(p1, load_pose(poses + 12ll * (f - 2)));
         store_pose(b.pred, pred);
-        for (int i = 0; i < 9; i++) R32[i] = (float)pred.R[i];
-        for (int i = 0; i < 3; i++) t32[i] = (float)pred.t[i];
+        pose_f32(pred.R, pred.t, R32, t32);
     }
     __syncthreads();
     const uint32_t slot = ref_slot(b.ctl, c), nk = b.ctl->kf_n[slot];
@@ -312,12 +130,8 @@ __device__ void project_frame(const TrackBufs& b, const TrackConst& c, int f, co
         bool front = false;
         float u = 0.f, v = 0.f;
         if (i < nk) {
-            const float X = b.kf_pts[3 * (o + i)], Y = b.kf_pts[3 * (o + i) + 1], Z = b.kf_pts[3 * (o + i) + 2];
-            float xc[3];
-            for (int r = 0; r < 3; r++) xc[r] = ((R32[3 * r] * X + R32[3 * r + 1] * Y) + R32[3 * r + 2] * Z) + t32[r];
-            front = xc[2] > 0.f;
-            u = (xc[0] / xc[2]) * c.fx + c.cx;
-            v = (xc[1] / xc[2]) * c.fy + c.cy;
+            const float X[3] = {b.kf_pts[3 * (o + i)], b.kf_pts[3 * (o + i) + 1], b.kf_pts[3 * (o + i) + 2]};
+            front = project_front(R32, t32, c.fx, c.fy, c.cx, c.cy, X, u, v);
         }
         uint32_t tot;
         const uint32_t pos = base + block_prefix<TT / 64>(front, wsum, &tot);
@@ -340,17 +154,6 @@ __device__ void project_frame(const TrackBufs& b, const TrackConst& c, int f, co
         b.nq[0] = base;
         b.nq[1] = b.nq[2] = 0;
     }
-}
-
-// Pass k + 1 runs when pass k ran and its result is weak (too few matches or ratio).
-__global__ void trk_weak(TrackBufs b, TrackConst c, int k)
-{
-    if (threadIdx.x != 0) return;
-    const uint32_t ns = b.ctl->ns, n = b.mn[k];
-    const bool weak = n < c.s.min_matches || (double)n / (double)max(ns, 1u) < c.s.small_match_ratio;
-    const uint32_t run = b.ctl->exec[k] && weak;
-    b.ctl->exec[k + 1] = run;
-    b.nq[k + 1] = run ? ns : 0u;
 }
 
 __global__ __launch_bounds__(TT) void trk_gather(TrackBufs b, TrackConst c, const mage_keypoint* fk, int f,
@@ -385,9 +188,7 @@ __global__ __launch_bounds__(TT) void trk_gather(TrackBufs b, TrackConst c, cons
         b.ctl->lost = lost;
         b.os1[0] = 0;
         b.os1[1] = lost ? 0u : n;
-        for (int i = 0; i < 3; i++) b.pos3[i] = (float)b.pred[9 + i];
-        for (int r = 0; r < 3; r++)
-            for (int cc = 0; cc < 3; cc++) b.r9[3 * cc + r] = (float)b.pred[3 * r + cc];  // column-major
+        to_bundler(b.pred, b.pred + 9, b.pos3, b.r9);
     }
 }
 
@@ -461,17 +262,11 @@ __device__ void lm_project_frame(const TrackBufs& b, const TrackConst& c)
         }
         return;
     }
+    // the pass-1 pose as pose BA 1 left it: its floats are the float view matrix (track.cpp casts
+    // the double pose made of them back to float: the same values)
     float R[9], t[3], C[3];
-    for (int r = 0; r < 3; r++)
-        for (int cc = 0; cc < 3; cc++) R[3 * r + cc] = b.r9_o1[3 * cc + r];
-    for (int i = 0; i < 3; i++) t[i] = b.pos3_o1[i];
-    for (int i = 0; i < 3; i++) {
-        float sum = 0.f;
-        for (int k = 0; k < 3; k++) sum = sum + R[3 * k + i] * -t[k];
-        C[i] = sum + 0.f;
-    }
-    const float fw[3] = {R[6], R[7], R[8]};
-    const float border = c.s.image_border, W = (float)c.s.width, H = (float)c.s.height;
+    from_bundler(b.pos3_o1, b.r9_o1, R, t);
+    world_position(R, t, C);
     const uint32_t first = b.ctl->kf_first, count = b.ctl->kf_count;
     uint32_t base = 0;
     for (uint32_t si = 0; si < count; si++) {
@@ -483,26 +278,9 @@ __device__ void lm_project_frame(const TrackBufs& b, const TrackConst& c)
             bool ok = i < n && !(is_ref && b.lm_visited[i]);
             float px = 0.f, py = 0.f;
             int oc = 0;
-            if (ok) {
-                const float* P = b.kf_pts + 3 * (o + i);
-                float cs[3];
-                for (int r = 0; r < 3; r++)
-                    cs[r] = (((0.f + R[3 * r] * P[0]) + R[3 * r + 1] * P[1]) + R[3 * r + 2] * P[2]) + t[r] * 1.f;
-                const float depth = cs[2], div = depth != 0 ? depth : 1.f;
-                px = (cs[0] / div) * c.fx + c.cx;
-                py = (cs[1] / div) * c.fy + c.cy;
-                ok = !(depth < 0) && border <= px && border <= py && px < W - border && py < H - border;
-                ok = ok && !(dot3f(b.kf_mvd + 3 * (o + i), fw) < c.s.min_view_cos);
-                const float dl[3] = {P[0] - C[0], P[1] - C[1], P[2] - C[2]};
-                const float d2 = (dl[0] * dl[0] + dl[1] * dl[1]) + dl[2] * dl[2];
-                const float dmin = b.kf_dmin[o + i], dmax = b.kf_dmax[o + i];
-                ok = ok && !(d2 < dmin * dmin || dmax * dmax < d2);
-                if (ok) {
-                    const float rr = sqrtf(d2) / dmin;
-                    oc = (int)roundf((float)log2((double)rr) / c.log2s - 0.5f);
-                    ok = oc >= 0 && oc <= (int)c.s.num_levels;
-                }
-            }
+            if (ok)
+                ok = local_map_candidate(R, t, C, c.fx, c.fy, c.cx, c.cy, c.s, c.log2s, b.kf_pts + 3 * (o + i),
+                                         b.kf_mvd + 3 * (o + i), b.kf_dmin[o + i], b.kf_dmax[o + i], px, py, oc);
             uint32_t tot;
             const uint32_t pos = base + block_prefix<TT / 64>(ok, wsum, &tot);
             if (ok && pos < c.qcap) {
@@ -572,14 +350,9 @@ __device__ void finish_frame(const TrackBufs& b, const TrackConst& c, int f, con
         if (c.s.local_map_keyframes > 0 && n_in < c.s.min_tracked) lost = true;
     }
     if (threadIdx.x == 0) {
-        DPose P;
-        if (lost) {
-            P = load_pose(b.pred);
-        } else {
-            for (int r = 0; r < 3; r++)
-                for (int cc = 0; cc < 3; cc++) P.R[3 * r + cc] = (double)b.r9_o2[3 * cc + r];
-            for (int i = 0; i < 3; i++) P.t[i] = (double)b.pos3_o2[i];
-        }
+        Pose P;  // pose BA 2's, or the prediction when lost (this order keeps the count loop above in VGPRs)
+        from_bundler(b.pos3_o2, b.r9_o2, P.R, P.t);
+        if (lost) P = load_pose(b.pred);
         store_pose(poses + 12ll * f, P);
         store_pose(sP, P);
         inliers[f] = lost ? 0u : n_in;
@@ -725,31 +498,7 @@ struct Pinned {
         n = m;
         return true;
     }
-    T& operator[](size_t i) { return p[i]; }
-    const T& operator[](size_t i) const { return p[i]; }
     T* data() { return p; }
-};
-
-struct HostRing {
-    uint32_t first = 0, count = 0, nk = 0, cap = 0, acap = 0;
-    uint32_t n[NKMAX], id[NKMAX], an[NKMAX];
-    // a page-locked byte-for-byte mirror of the device ring's fields (one DMA copy each way per
-    // window); the arrays below point into it at the device layout's offsets
-    Pinned<uint8_t> mirror;
-    double* pose = nullptr;       // 12 per slot
-    mage_keypoint* kp = nullptr;  // cap per slot
-    float *pts = nullptr, *mvd = nullptr, *dmin = nullptr, *dmax = nullptr;
-    uint32_t* ref = nullptr;
-    uint8_t *own = nullptr, *aalive = nullptr;
-    int4* assoc = nullptr;
-    Pinned<uint32_t> zero;  // the halt word's clear value
-};
-
-struct LocalBA {  // MappingWorker's CurrentLambda and CosVisThreashold, persisted across the windows
-    bool have_lambda = false;
-    float lambda = 0.f;
-    bool have_theta = false;
-    uint32_t theta = 0;
 };
 
 struct BundlerHandle {  // a fresh BundlerLib per window (BundleAdjust.cpp MakeBundler)
@@ -760,240 +509,42 @@ struct BundlerHandle {  // a fresh BundlerLib per window (BundleAdjust.cpp MakeB
     }
 };
 
-void host_world_position(const double* R, const double* t, float C[3])
-{
-    for (int i = 0; i < 3; i++) {
-        float sum = 0.f;
-        for (int k = 0; k < 3; k++) sum = sum + (float)R[3 * k + i] * -(float)t[k];
-        C[i] = sum + 0.f;
-    }
-}
+struct BaSolution {
+    std::vector<uint32_t> outl;  // outlier observations (indices into the window's), nout of them
+    uint32_t nout = 0;
+    std::vector<float> pos, r9, xyz;  // GetPose / GetPoint
+};
 
-float host_dot3(const float* a, const float* b) { return ((0.f + a[0] * b[0]) + a[1] * b[1]) + a[2] * b[2]; }
-
-float bits_float(int v)
+// BundlerLib on one window (tracking.py run_bundler); the lambda persisted across windows
+mage_status solve_window(const BaWindow& w, const TrackConst& c, LocalBA& L, int device, BundlerHandle& H, BaSolution& o,
+                         PhaseClock& prof)
 {
-    float f;
-    std::memcpy(&f, &v, 4);
-    return f;
-}
-
-// tracking.point_attributes for point i of a slot
-void host_point_attributes(HostRing& R, uint32_t slot, uint32_t i, const TrackConst& c)
-{
-    const size_t o = (size_t)slot * R.cap + i;
-    float C[3];
-    host_world_position(&R.pose[12 * slot], &R.pose[12 * slot + 9], C);
-    const float* P = &R.pts[3 * o];
-    float v[3] = {P[0] - C[0], P[1] - C[1], P[2] - C[2]};
-    const float d = sqrtf(host_dot3(v, v));
-    if (d != 0) {
-        const float inv = 1.f / d;
-        for (float& x : v) x = x * inv;
-    }
-    const float d2 = sqrtf(host_dot3(v, v));
-    if (d2 != 0) {
-        const float inv = 1.f / d2;
-        for (float& x : v) x = x * inv;
-    }
-    for (int j = 0; j < 3; j++) R.mvd[3 * o + j] = v[j];
-    const float dl[3] = {C[0] - P[0], C[1] - P[1], C[2] - P[2]};
-    const float dist = sqrtf((dl[0] * dl[0] + dl[1] * dl[1]) + dl[2] * dl[2]);
-    const int oc = std::min(std::max(R.kp[o].octave, 0), 7);
-    R.dmin[o] = dist * c.fmin[oc];
-    R.dmax[o] = dist * c.fmax[oc];
-}
-
-// One local BA on the ring (on the host copy); returns the outlier count (UINT32_MAX: no window).
-mage_status host_local_ba(HostRing& R, const TrackConst& c, LocalBA& L, int device, uint32_t* n_out,
-                          std::vector<uint8_t>& slot_changed, PhaseClock& prof)
-{
-    *n_out = 0xFFFFFFFFu;
-    const uint32_t nr = R.count;
-    if (nr < 2) return MAGE_OK;
-    uint32_t slot_of[NKMAX];
-    for (uint32_t r = 0; r < nr; r++) slot_of[r] = (R.first + r) % R.nk;
-    auto pos_of = [&](int id) -> int {
-        for (uint32_t r = 0; r < nr; r++)
-            if ((int)R.id[slot_of[r]] == id) return (int)r;
-        return -1;
-    };
-    struct Obs {
-        uint32_t cam, owner, idx;
-        float u, v;
-        uint32_t kind, src;  // 0: own (point index), 1: association (entry)
-    };
-    std::vector<Obs> obs;
-    obs.reserve((size_t)nr * R.cap * 2);
-    for (uint32_t r = 0; r < nr; r++) {
-        const uint32_t sl = slot_of[r];
-        const size_t o = (size_t)sl * R.cap;
-        for (uint32_t i = 0; i < R.n[sl]; i++)
-            if (R.own[o + i]) obs.push_back({r, r, i, R.kp[o + i].x, R.kp[o + i].y, 0, i});
-        const size_t ao = (size_t)sl * R.acap;
-        for (uint32_t a = 0; a < R.an[sl]; a++) {
-            const int4 e = R.assoc[ao + a];
-            const int ow = pos_of(e.x);
-            if (R.aalive[ao + a] && ow >= 0)
-                obs.push_back({r, (uint32_t)ow, (uint32_t)e.y, bits_float(e.z), bits_float(e.w), 1, a});
-        }
-    }
-    // the window's points, ascending (owner, index): a dense (ring position, index) map instead of
-    // a sorted key list (the window build runs between frames, on the loop's critical path)
-    std::vector<int32_t> pmap((size_t)nr * R.cap, -1);
-    uint32_t freemask = 0;
-    if (c.s.ba_free_keyframes > 0) {
-        // the newest ba_free_keyframes free, the oldest fixed (at least one); the points they observe
-        const uint32_t nfix = nr > c.s.ba_free_keyframes ? nr - c.s.ba_free_keyframes : 1u;
-        for (uint32_t r = nfix; r < nr; r++) freemask |= 1u << r;
-        for (const Obs& ob : obs)
-            if (ob.cam >= nfix) pmap[(size_t)ob.owner * R.cap + ob.idx] = 0;
-    } else {
-        // GetMapPointsAndDistantKeyframes (ThreadSafeMap.cpp:888-957; tracking.py covisible_window):
-        // per point the mask of ring keyframes observing it; the covisibility weight of keyframe r
-        // to the newest one is the count of points both observe (CovisibilityGraph.cpp:131-170)
-        std::vector<uint8_t> seen((size_t)nr * R.cap, 0);
-        for (const Obs& ob : obs) seen[(size_t)ob.owner * R.cap + ob.idx] |= (uint8_t)(1u << ob.cam);
-        const uint32_t last = nr - 1;
-        uint32_t weight[NKMAX] = {};
-        for (uint8_t m : seen)
-            if (m >> last & 1u)
-                for (uint32_t r = 0; r < last; r++) weight[r] += m >> r & 1u;
-        uint32_t theta = L.have_theta ? L.theta : c.s.covis_min_threshold, kc = 0;
-        for (uint32_t step = 0; step <= c.s.covis_max_steps; step++) {
-            kc = 1u << last;
-            for (uint32_t r = 0; r < last; r++)
-                if (weight[r] >= theta) kc |= 1u << r;
-            size_t n_assoc = 0;
-            for (const Obs& ob : obs) n_assoc += (seen[(size_t)ob.owner * R.cap + ob.idx] & kc) != 0;
-            if (n_assoc > c.s.ba_upper_connections) {
-                theta += c.s.covis_ba_step;
-                continue;
-            }
-            if (n_assoc < c.s.ba_lower_connections && theta > c.s.covis_min_threshold) {
-                theta -= c.s.covis_ba_step;
-                continue;
-            }
-            break;
-        }
-        L.theta = theta;
-        L.have_theta = true;
-        for (size_t q = 0; q < seen.size(); q++)
-            if (seen[q] & kc) pmap[q] = 0;
-        for (uint32_t r = 0; r < nr; r++)  // the map's first keyframe stays fixed (ThreadSafeMap.cpp:89)
-            if ((kc >> r & 1u) && R.id[slot_of[r]] != 0) freemask |= 1u << r;
-    }
-    std::vector<uint64_t> keys;
-    for (uint32_t r = 0; r < nr; r++)
-        for (uint32_t i = 0; i < R.cap; i++)
-            if (pmap[(size_t)r * R.cap + i] == 0) {
-                pmap[(size_t)r * R.cap + i] = (int32_t)keys.size();
-                keys.push_back((uint64_t)r << 32 | i);
-            }
-    std::vector<Obs> kept;
-    std::vector<uint32_t> cam, pt;
-    std::vector<float> uv, info;
-    kept.reserve(obs.size());
-    cam.reserve(obs.size());
-    pt.reserve(obs.size());
-    uv.reserve(2 * obs.size());
-    for (const Obs& ob : obs) {
-        const int32_t p = pmap[(size_t)ob.owner * R.cap + ob.idx];
-        if (p < 0) continue;
-        kept.push_back(ob);
-        cam.push_back(ob.cam);
-        pt.push_back((uint32_t)p);
-        uv.push_back(ob.u);
-        uv.push_back(ob.v);
-    }
-    if (kept.empty() || freemask == 0) return MAGE_OK;
-    const uint32_t P = (uint32_t)keys.size(), E = (uint32_t)kept.size();
-    std::vector<float> xyz(3ull * P);
-    std::vector<uint32_t> pref(P);
-    for (uint32_t q = 0; q < P; q++) {
-        const uint32_t sl = slot_of[keys[q] >> 32], i = (uint32_t)(keys[q] & 0xFFFFFFFFu);
-        const size_t o = (size_t)sl * R.cap + i;
-        for (int j = 0; j < 3; j++) xyz[3 * q + j] = R.pts[3 * o + j];
-        pref[q] = R.ref[o];
-    }
-    for (uint32_t e = 0; e < E; e++) info.push_back(refinement_confidence(pref[pt[e]]));
-    // cameras: view-space t, Eigen column-major R, {cx, cy, fx, fy}; the oldest fixed
-    std::vector<float> pos3(3 * nr), r9(9 * nr), intr(4 * nr);
-    std::vector<uint8_t> fixed(nr, 0);
-    for (uint32_t r = 0; r < nr; r++) fixed[r] = (freemask >> r & 1u) ? 0 : 1;
-    for (uint32_t r = 0; r < nr; r++) {
-        const double* ps = &R.pose[12 * slot_of[r]];
-        for (int i = 0; i < 3; i++) pos3[3 * r + i] = (float)ps[9 + i];
-        for (int rr = 0; rr < 3; rr++)
-            for (int cc = 0; cc < 3; cc++) r9[9 * r + 3 * cc + rr] = (float)ps[3 * rr + cc];
-        intr[4 * r] = (float)c.K[2];
-        intr[4 * r + 1] = (float)c.K[3];
-        intr[4 * r + 2] = (float)c.K[0];
-        intr[4 * r + 3] = (float)c.K[1];
-    }
-    // NumStepsPerRun / Huber width by the connectivity ratio (MappingWorker.cpp:254-263)
-    const uint32_t ratio = c.s.ba_upper_connections / E;
-    uint32_t steps = c.s.ba_steps_per_run;
-    float huber = c.s.ba_huber;
-    if (ratio > 0) {
-        steps = steps * (uint32_t)((float)ratio * c.s.ba_low_connectivity_scale);
-        huber = huber * powf(c.s.ba_huber_scale, (float)ratio);
-    }
-    const std::vector<float> hw(std::max(steps, 1u), huber);
+    const uint32_t nr = w.nr, P = (uint32_t)w.keys.size(), E = (uint32_t)w.kept.size();
+    const std::vector<float> hw(std::max(w.steps, 1u), w.huber);
     mage_status st;
-    prof.mark("window");
-    BundlerHandle H;
     if ((st = mage_ba_create(0, device, &H.ba)) != MAGE_OK) return st;
     prof.mark("create");
     if (L.have_lambda && (st = mage_ba_set_lambda(H.ba, L.lambda)) != MAGE_OK) return st;
-    if ((st = mage_ba_set_cameras(H.ba, nr, pos3.data(), r9.data(), intr.data(), fixed.data())) != MAGE_OK ||
-        (st = mage_ba_set_points(H.ba, P, xyz.data())) != MAGE_OK ||
-        (st = mage_ba_set_observations(H.ba, E, uv.data(), cam.data(), pt.data(), info.data())) != MAGE_OK)
+    if ((st = mage_ba_set_cameras(H.ba, nr, w.pos3.data(), w.r9.data(), w.intr.data(), w.fixed.data())) != MAGE_OK ||
+        (st = mage_ba_set_points(H.ba, P, w.xyz.data())) != MAGE_OK ||
+        (st = mage_ba_set_observations(H.ba, E, w.uv.data(), w.cam.data(), w.pt.data(), w.info.data())) != MAGE_OK)
         return st;
     prof.mark("setters");
-    std::vector<uint32_t> outl(E);
-    uint32_t nout = 0;
+    o.outl.resize(E);
     float ms = 0.f;
-    if ((st = mage_ba_step(H.ba, hw.data(), (uint32_t)hw.size(), c.s.ba_max_outlier_error, outl.data(), E, &nout, &ms)) !=
-        MAGE_OK)
+    if ((st = mage_ba_step(H.ba, hw.data(), (uint32_t)hw.size(), c.s.ba_max_outlier_error, o.outl.data(), E, &o.nout,
+                           &ms)) != MAGE_OK)
         return st;
     prof.mark("step");
-    std::vector<float> pos_o(3 * nr), r9_o(9 * nr), xyz_o(3ull * P);
+    o.pos.resize(3 * nr);
+    o.r9.resize(9 * nr);
+    o.xyz.resize(3ull * P);
     float lam = 0.f;
-    if ((st = mage_ba_get_poses(H.ba, pos_o.data(), r9_o.data())) != MAGE_OK ||
-        (st = mage_ba_get_points(H.ba, xyz_o.data())) != MAGE_OK || (st = mage_ba_get_lambda(H.ba, &lam)) != MAGE_OK)
+    if ((st = mage_ba_get_poses(H.ba, o.pos.data(), o.r9.data())) != MAGE_OK ||
+        (st = mage_ba_get_points(H.ba, o.xyz.data())) != MAGE_OK || (st = mage_ba_get_lambda(H.ba, &lam)) != MAGE_OK)
         return st;
     L.have_lambda = true;
     L.lambda = std::max(lam, c.s.min_lambda);
-    // AdjustPosesAndMapPoints: outlier associations, free poses, points (+ refinement), attributes
-    for (uint32_t k = 0; k < std::min(nout, E); k++) {
-        const Obs& ob = kept[outl[k]];
-        const uint32_t sl = slot_of[ob.cam];
-        if (ob.kind == 0)
-            R.own[(size_t)sl * R.cap + ob.src] = 0;
-        else
-            R.aalive[(size_t)sl * R.acap + ob.src] = 0;
-        slot_changed[sl] = 1;
-    }
-    for (uint32_t r = 0; r < nr; r++) {
-        if (!(freemask >> r & 1u)) continue;
-        double* ps = &R.pose[12 * slot_of[r]];
-        for (int rr = 0; rr < 3; rr++)
-            for (int cc = 0; cc < 3; cc++) ps[3 * rr + cc] = (double)r9_o[9 * r + 3 * cc + rr];
-        for (int i = 0; i < 3; i++) ps[9 + i] = (double)pos_o[3 * r + i];
-        slot_changed[slot_of[r]] = 1;
-    }
-    for (uint32_t q = 0; q < P; q++) {
-        const uint32_t sl = slot_of[keys[q] >> 32], i = (uint32_t)(keys[q] & 0xFFFFFFFFu);
-        const size_t o = (size_t)sl * R.cap + i;
-        for (int j = 0; j < 3; j++) R.pts[3 * o + j] = xyz_o[3 * q + j];
-        R.ref[o] += 1;
-        slot_changed[sl] = 1;
-    }
-    for (uint32_t q = 0; q < P; q++)
-        host_point_attributes(R, slot_of[keys[q] >> 32], (uint32_t)(keys[q] & 0xFFFFFFFFu), c);
-    prof.mark("get + apply");
-    *n_out = nout;
     return MAGE_OK;
 }
 
@@ -1018,108 +569,8 @@ extern "C" mage_status mage_track_sequence_device(const mage_keypoint* d_kp, con
     // count (TrackLocalMap.cpp:473-475); the setting only names its count-0 value
     MAGE_REQUIRE(s->refinement_info == refinement_confidence(0), MAGE_EINVAL,
                  "refinement_info must be MapPointRefinementConfidence(0) = 1 - 1/1.5^2");
-    const size_t cap = pitch;
     const uint32_t NK = std::max(s->local_map_keyframes, 1u);
-    const size_t qcap = s->local_map_keyframes > 0 ? (size_t)NK * cap : 0;  // local-map queries
-    const size_t c2 = cap + qcap;                                           // pose-BA 2 observations
-    const size_t acap = c2;                                                 // associations per keyframe
-    // one device allocation for the per-call scratch and outputs
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off = al(off + bytes);
-        return o;
-    };
-    const size_t o_ctl = take(sizeof(Ctl)), o_pred = take(12 * 8), o_kfkp = take(28 * cap * NK),
-                 o_kfd = take(32 * cap * NK), o_kfp = take(12 * cap * NK), o_kfv = take(12 * cap * NK),
-                 o_kfdn = take(4 * cap * NK), o_kfdx = take(4 * cap * NK), o_kfps = take(96 * NK),
-                 o_kfr = take(4 * cap * NK), o_kfo = take(cap * NK), o_kfa = take(16 * acap * NK), o_kfaa = take(acap * NK),
-                 o_s1 = take(8 * cap), o_s2 = take(8 * c2), o_i1 = take(4 * cap), o_lqs = take(8 * qcap),
-                 o_lqi = take(4 * qcap), o_qkp = take(28 * cap), o_qd = take(32 * cap),
-                 o_qp = take(8 * cap), o_sel = take(4 * cap), o_nq = take(16), o_m = take(3 * 16 * cap), o_mn = take(16),
-                 o_rs = take(4 * cap), o_rst = take(4), o_pos = take(12), o_r9 = take(36), o_in = take(16),
-                 o_os1 = take(8), o_os2 = take(8), o_p1 = take(12 * cap), o_u1 = take(8 * cap), o_p2 = take(12 * c2),
-                 o_u2 = take(8 * c2), o_inf = take(4 * c2), o_po1 = take(12), o_ro1 = take(36), o_po2 = take(12),
-                 o_ro2 = take(36), o_out1 = take(cap), o_out2 = take(c2), o_msq = take(8),
-                 o_lmm = take(4 * 4096 / 32), o_lmv = take(cap), o_lmh = take(4 * cap), o_lqp = take(8 * qcap),
-                 o_lqo = take(4 * qcap), o_lqh = take(4 * qcap), o_lqd = take(32 * qcap), o_lqt = take(12 * qcap),
-                 o_lres = take(4 * qcap), o_lst = take(4), o_lscr = take(local_map_scratch_bytes((uint32_t)qcap)),
-                 o_poses = take(96ull * frames), o_mt = take(4ull * frames), o_il = take(4ull * frames),
-                 o_kf = take(frames), o_bk = take(8ull * pitch * BAND_SLOTS), o_bxy = take(8ull * pitch * BAND_SLOTS),
-                 o_bd = take(32ull * pitch * BAND_SLOTS);
-    DeviceBuffer buf;
-    mage_status r = buf.reserve(off);
-    if (r != MAGE_OK) return r;
-    char* d = buf.as<char>();
-    TrackBufs b{};
-    b.ctl = reinterpret_cast<Ctl*>(d + o_ctl);
-    b.pred = reinterpret_cast<double*>(d + o_pred);
-    b.kf_kp = reinterpret_cast<mage_keypoint*>(d + o_kfkp);
-    b.kf_desc = reinterpret_cast<uint8_t*>(d + o_kfd);
-    b.kf_pts = reinterpret_cast<float*>(d + o_kfp);
-    b.kf_mvd = reinterpret_cast<float*>(d + o_kfv);
-    b.kf_dmin = reinterpret_cast<float*>(d + o_kfdn);
-    b.kf_dmax = reinterpret_cast<float*>(d + o_kfdx);
-    b.kf_pose = reinterpret_cast<double*>(d + o_kfps);
-    b.kf_ref = reinterpret_cast<uint32_t*>(d + o_kfr);
-    b.kf_own = reinterpret_cast<uint8_t*>(d + o_kfo);
-    b.kf_assoc = reinterpret_cast<int4*>(d + o_kfa);
-    b.kf_aalive = reinterpret_cast<uint8_t*>(d + o_kfaa);
-    b.src1 = reinterpret_cast<int2*>(d + o_s1);
-    b.src2 = reinterpret_cast<int2*>(d + o_s2);
-    b.info1 = reinterpret_cast<float*>(d + o_i1);
-    b.lm_qsrc = reinterpret_cast<int2*>(d + o_lqs);
-    b.lm_qinfo = reinterpret_cast<float*>(d + o_lqi);
-    b.lm_mask = reinterpret_cast<uint32_t*>(d + o_lmm);
-    b.lm_visited = reinterpret_cast<uint8_t*>(d + o_lmv);
-    b.lm_hide = reinterpret_cast<int32_t*>(d + o_lmh);
-    b.lm_qpos = reinterpret_cast<float*>(d + o_lqp);
-    b.lm_qoct = reinterpret_cast<int32_t*>(d + o_lqo);
-    b.lm_qhide = reinterpret_cast<int32_t*>(d + o_lqh);
-    b.lm_qdesc = reinterpret_cast<uint8_t*>(d + o_lqd);
-    b.lm_qpt = reinterpret_cast<float*>(d + o_lqt);
-    b.lm_res = reinterpret_cast<int32_t*>(d + o_lres);
-    b.lm_status = reinterpret_cast<uint32_t*>(d + o_lst);
-    b.lm_scratch = d + o_lscr;
-    b.qkp = reinterpret_cast<mage_keypoint*>(d + o_qkp);
-    b.qdesc = reinterpret_cast<uint8_t*>(d + o_qd);
-    b.qpos = reinterpret_cast<float*>(d + o_qp);
-    b.sel = reinterpret_cast<uint32_t*>(d + o_sel);
-    b.nq = reinterpret_cast<uint32_t*>(d + o_nq);
-    b.m = reinterpret_cast<mage_dmatch*>(d + o_m);
-    b.mn = reinterpret_cast<uint32_t*>(d + o_mn);
-    b.pos3 = reinterpret_cast<float*>(d + o_pos);
-    b.r9 = reinterpret_cast<float*>(d + o_r9);
-    b.intr4 = reinterpret_cast<float*>(d + o_in);
-    b.os1 = reinterpret_cast<uint32_t*>(d + o_os1);
-    b.os2 = reinterpret_cast<uint32_t*>(d + o_os2);
-    b.pts1 = reinterpret_cast<float*>(d + o_p1);
-    b.uv1 = reinterpret_cast<float*>(d + o_u1);
-    b.pts2 = reinterpret_cast<float*>(d + o_p2);
-    b.uv2 = reinterpret_cast<float*>(d + o_u2);
-    b.info2 = reinterpret_cast<float*>(d + o_inf);
-    b.pos3_o1 = reinterpret_cast<float*>(d + o_po1);
-    b.r9_o1 = reinterpret_cast<float*>(d + o_ro1);
-    b.pos3_o2 = reinterpret_cast<float*>(d + o_po2);
-    b.r9_o2 = reinterpret_cast<float*>(d + o_ro2);
-    b.out1 = reinterpret_cast<uint8_t*>(d + o_out1);
-    b.out2 = reinterpret_cast<uint8_t*>(d + o_out2);
-    b.msq = reinterpret_cast<float*>(d + o_msq);
-    int32_t* rscratch = reinterpret_cast<int32_t*>(d + o_rs);
-    uint32_t* rstatus = reinterpret_cast<uint32_t*>(d + o_rst);
-    double* dposes = reinterpret_cast<double*>(d + o_poses);
-    uint32_t* dmt = reinterpret_cast<uint32_t*>(d + o_mt);
-    uint32_t* dil = reinterpret_cast<uint32_t*>(d + o_il);
-    uint8_t* dkf = reinterpret_cast<uint8_t*>(d + o_kf);
-    // RadiusMatch band indices (each frame is matched up to 3 times, so its index is built once):
-    // a ring of BAND_SLOTS frames, built BAND_CHUNK frames at a time by the enqueue of a chunk's
-    // first frame — the loop runs at most DEPTH frames ahead, so a chunk's slots are free again
-    // when the chunk two ahead is built, and device memory does not grow with the sequence
-    unsigned long long* bkeys = reinterpret_cast<unsigned long long*>(d + o_bk);
-    float* bxy = reinterpret_cast<float*>(d + o_bxy);
-    uint32_t* bdesc = reinterpret_cast<uint32_t*>(d + o_bd);
-
+    const size_t qcap = s->local_map_keyframes > 0 ? (size_t)NK * pitch : 0;  // local-map queries
     TrackConst c{};
     c.fx = (float)K[0];
     c.fy = (float)K[1];
@@ -1131,12 +582,20 @@ extern "C" mage_status mage_track_sequence_device(const mage_keypoint* d_kp, con
     c.cap = pitch;
     c.nk = NK;
     c.qcap = (uint32_t)qcap;
-    c.acap = (uint32_t)acap;
-    for (int o = 0; o < 8; o++) {
-        c.fmax[o] = powf(s->scale_factor, (float)s->num_levels - ((float)o + 0.5f));
-        c.fmin[o] = powf(s->scale_factor, 0.f - ((float)o + 0.5f));
-    }
-    c.log2s = (float)std::log2((double)s->scale_factor);
+    c.acap = (uint32_t)(pitch + qcap);  // associations per keyframe = pose-BA 2 observations
+    octave_factors(s->scale_factor, s->num_levels, c.fmax, c.fmin, &c.log2s);
+    // one device allocation for the per-call scratch and outputs: track_bufs.hpp's table, run
+    // once at base 0 for the size and the ring's range, once at the allocation
+    const size_t lm_bytes = local_map_scratch_bytes(c.qcap);
+    TrackBlock blk{};
+    const BlockBinder lay = track_block(blk, c, frames, lm_bytes, nullptr);
+    MAGE_REQUIRE(lay.ring_contiguous, MAGE_EINVAL, "track block: the keyframe ring's buffers are not consecutive");
+    DeviceBuffer buf;
+    mage_status r = buf.reserve(lay.bytes);
+    if (r != MAGE_OK) return r;
+    char* d = buf.as<char>();
+    track_block(blk, c, frames, lm_bytes, d);
+    TrackBufs& b = blk.b;
     const float e1 = (float)(s->initial_max_error * s->initial_max_error);
     const float e2 = (float)(s->final_max_error * s->final_max_error);
 
@@ -1145,10 +604,11 @@ extern "C" mage_status mage_track_sequence_device(const mage_keypoint* d_kp, con
         buf.release();
         return st2;
     };
-    if (hipMemsetAsync(d, 0, off, st) != hipSuccess ||
-        hipMemcpyAsync(dposes, first_pose, 96, hipMemcpyHostToDevice, st) != hipSuccess)
+    if (hipMemsetAsync(d, 0, lay.bytes, st) != hipSuccess ||
+        hipMemcpyAsync(blk.poses, first_pose, 96, hipMemcpyHostToDevice, st) != hipSuccess)
         return fail(MAGE_EDEVICE);
-    hipLaunchKernelGGL(trk_init, dim3(1), dim3(TT), 0, st, b, c, d_kp, d_desc, d_n, dposes, dmt, dil, dkf, rstatus);
+    hipLaunchKernelGGL(trk_init, dim3(1), dim3(TT), 0, st, b, c, d_kp, d_desc, d_n, blk.poses, blk.matches,
+                       blk.inliers, blk.keyframe, blk.rstatus);
     const float radius[3] = {s->search_radius, s->wider_search_radius, s->extra_wider_search_radius};
     // project: frame f's prediction is its own launch (first frame, first frame after a local BA);
     // otherwise the previous frame's trk_finish_project made it
@@ -1160,23 +620,25 @@ extern "C" mage_status mage_track_sequence_device(const mage_keypoint* d_kp, con
         mage_status rr;
         if (f == 1 || f % BAND_CHUNK == 0) {  // build the band indices of frames [f, next chunk)
             const uint32_t end = std::min(frames, (f / BAND_CHUNK + 1) * BAND_CHUNK);
-            if ((rr = radius_band_index_launch(fk, fd, nf, (int64_t)pitch, end - f, bkeys + slot * pitch,
-                                               bxy + 2 * slot * pitch, bdesc + 8 * slot * pitch, st)) != MAGE_OK)
+            if ((rr = radius_band_index_launch(fk, fd, nf, (int64_t)pitch, end - f, blk.bkeys + slot * pitch,
+                                               blk.bxy + 2 * slot * pitch, blk.bdesc + 8 * slot * pitch, st)) !=
+                MAGE_OK)
                 return rr;
         }
-        if (project) launch("track.project", trk_project, dim3(1), dim3(TT), 0, st, b, c, (int)f, (const double*)dposes);
+        if (project)
+            launch("track.project", trk_project, dim3(1), dim3(TT), 0, st, b, c, (int)f, (const double*)blk.poses);
         for (int k = 0; k < 3; k++) {
-            // passes 0 and 1 end with the fallback decision for the next (trk_weak's, in the pass's
-            // last workgroup: one dependent launch less per pass)
+            // passes 0 and 1 end with the fallback decision for the next (radius_pass_weak, in the
+            // pass's last workgroup: one dependent launch less per pass)
             const RadiusFollow follow{&b.ctl->ns, b.ctl->exec, b.nq + k + 1, k, s->min_matches, s->small_match_ratio};
             rr = radius_match_indexed(b.qkp, k < 2 ? b.qpos : nullptr, b.qdesc, (int64_t)pitch, b.nq + k, fk, fd,
-                                      (int64_t)pitch, nf, bkeys + slot * pitch, bxy + 2 * slot * pitch,
-                                      bdesc + 8 * slot * pitch, 1, radius[k], s->max_hamming, s->min_hamming_difference,
-                                      rscratch, b.m + (size_t)k * pitch, pitch, b.mn + k, rstatus, st,
-                                      k < 2 ? &follow : nullptr);
+                                      (int64_t)pitch, nf, blk.bkeys + slot * pitch, blk.bxy + 2 * slot * pitch,
+                                      blk.bdesc + 8 * slot * pitch, 1, radius[k], s->max_hamming,
+                                      s->min_hamming_difference, blk.rscratch, b.m + (size_t)k * pitch, pitch,
+                                      b.mn + k, blk.rstatus, st, k < 2 ? &follow : nullptr);
             if (rr != MAGE_OK) return rr;
         }
-        launch("track.gather", trk_gather, dim3(1), dim3(TT), 0, st, b, c, fk, (int)f, dmt);
+        launch("track.gather", trk_gather, dim3(1), dim3(TT), 0, st, b, c, fk, (int)f, blk.matches);
         rr = mage_ba_pose_batch_device(1, b.pos3, b.r9, b.intr4, b.os1, b.pts1, b.uv1, b.info1, s->initial_steps,
                                        s->initial_huber, e1, b.pos3_o1, b.r9_o1, nullptr, b.out1, b.msq, nullptr,
                                        stream);
@@ -1199,7 +661,7 @@ extern "C" mage_status mage_track_sequence_device(const mage_keypoint* d_kp, con
             la.min_diff = s->local_min_hamming_difference;
             la.result = b.lm_res;
             la.status = b.lm_status;
-            la.keys = bkeys + slot * pitch;
+            la.keys = blk.bkeys + slot * pitch;
             if ((rr = local_map_match_launch(la, b.lm_scratch, st)) != MAGE_OK) return rr;
             launch("track.lm_assemble", trk_lm_assemble, dim3(1), dim3(TT), 0, st, b, fk);
         } else {
@@ -1209,8 +671,8 @@ extern "C" mage_status mage_track_sequence_device(const mage_keypoint* d_kp, con
                                        s->final_huber, e2, b.pos3_o2, b.r9_o2, nullptr, b.out2, b.msq + 1, nullptr,
                                        stream);
         if (rr != MAGE_OK) return rr;
-        launch("track.finish", trk_finish_project, dim3(1), dim3(TT), 0, st, b, c, (int)f, fk, fd, nf, dposes, dil,
-               dkf, rstatus, (int)(f + 1 < frames));
+        launch("track.finish", trk_finish_project, dim3(1), dim3(TT), 0, st, b, c, (int)f, fk, fd, nf, blk.poses,
+               blk.inliers, blk.keyframe, blk.rstatus, (int)(f + 1 < frames));
         return MAGE_OK;
     };
     if (ba_outliers)
@@ -1232,10 +694,10 @@ extern "C" mage_status mage_track_sequence_device(const mage_keypoint* d_kp, con
         hp[0] = 0;
         hp[1] = 0;
         b.prog = prog.device<uint32_t>();
-        HostRing R;
-        R.nk = NK;
-        R.cap = (uint32_t)cap;
-        R.acap = (uint32_t)acap;
+        // a page-locked mirror of the device ring (one DMA copy each way per window), the halt-clear word
+        Pinned<uint8_t> mirror;
+        Pinned<uint32_t> zero;
+        const size_t mbytes = lay.ring_end - lay.ring_begin;
         LocalBA L;
         PhaseClock prof;
         {
@@ -1267,36 +729,24 @@ extern "C" mage_status mage_track_sequence_device(const mage_keypoint* d_kp, con
             prof.mark("drain");
             Ctl hc;
             if (hipMemcpy(&hc, b.ctl, sizeof(Ctl), hipMemcpyDeviceToHost) != hipSuccess) return fail(MAGE_EDEVICE);
-            R.first = hc.kf_first;
-            R.count = hc.kf_count;
-            for (uint32_t k = 0; k < NK; k++) {
-                R.n[k] = hc.kf_n[k];
-                R.id[k] = hc.kf_id[k];
-                R.an[k] = hc.kf_an[k];
-            }
-            // the ring's fields are consecutive in the device block from kf_kp to kf_aalive
-            const size_t mbytes = o_kfaa + acap * NK - o_kfkp;
-            if (!R.mirror.resize(mbytes) || !R.zero.resize(1)) return fail(MAGE_ENOMEM);
-            uint8_t* hm = R.mirror.data();
-            R.kp = reinterpret_cast<mage_keypoint*>(hm + (o_kfkp - o_kfkp));
-            R.pts = reinterpret_cast<float*>(hm + (o_kfp - o_kfkp));
-            R.mvd = reinterpret_cast<float*>(hm + (o_kfv - o_kfkp));
-            R.dmin = reinterpret_cast<float*>(hm + (o_kfdn - o_kfkp));
-            R.dmax = reinterpret_cast<float*>(hm + (o_kfdx - o_kfkp));
-            R.pose = reinterpret_cast<double*>(hm + (o_kfps - o_kfkp));
-            R.ref = reinterpret_cast<uint32_t*>(hm + (o_kfr - o_kfkp));
-            R.own = hm + (o_kfo - o_kfkp);
-            R.assoc = reinterpret_cast<int4*>(hm + (o_kfa - o_kfkp));
-            R.aalive = hm + (o_kfaa - o_kfkp);
-            R.zero[0] = 0;
-            if (hipMemcpyAsync(hm, d + o_kfkp, mbytes, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            if (!mirror.resize(mbytes) || !zero.resize(1)) return fail(MAGE_ENOMEM);
+            *zero.data() = 0;
+            if (hipMemcpyAsync(mirror.data(), d + lay.ring_begin, mbytes, hipMemcpyDeviceToHost, st) != hipSuccess ||
                 hipStreamSynchronize(st) != hipSuccess)
                 return fail(MAGE_EDEVICE);
+            HostRing R = host_ring(c, frames, lm_bytes, mirror.data(), hc);
             prof.mark("ring D2H");
             std::fill(changed.begin(), changed.end(), 0);
-            uint32_t nout = 0;
-            if ((r = host_local_ba(R, c, L, dev, &nout, changed, prof)) != MAGE_OK) return fail(r);
-            if (ba_outliers) ba_outliers[f] = nout;
+            const BaWindow w = build_window(R, c, L);  // tracking.py local_bundle_adjust, on the host copy
+            if (w.valid) {
+                prof.mark("window");
+                BundlerHandle H;  // destroyed at the end of this block, after the apply
+                BaSolution o;
+                if ((r = solve_window(w, c, L, dev, H, o, prof)) != MAGE_OK) return fail(r);
+                apply_window(R, c, w, o.outl.data(), o.nout, o.pos.data(), o.r9.data(), o.xyz.data(), changed);
+                prof.mark("get + apply");
+                if (ba_outliers) ba_outliers[f] = o.nout;
+            }
             // write back the changed slots, the frame's pose (= its keyframe's) and clear the halt:
             // queued on the stream ahead of the next frames (the ring's host copy is not touched
             // again before the next window's drain)
@@ -1304,12 +754,13 @@ extern "C" mage_status mage_track_sequence_device(const mage_keypoint* d_kp, con
             for (uint32_t k = 0; k < NK; k++) any = any || changed[k];
             // one copy of the mirror from the points on (kf_pts .. kf_aalive: every field the window
             // changes; the unchanged slots and the associations go back as they came)
-            if (any && hipMemcpyAsync(d + o_kfp, R.mirror.data() + (o_kfp - o_kfkp), o_kfaa + acap * NK - o_kfp,
-                                      hipMemcpyHostToDevice, st) != hipSuccess)
+            if (any && hipMemcpyAsync(d + lay.moved_begin, mirror.data() + (lay.moved_begin - lay.ring_begin),
+                                      lay.ring_end - lay.moved_begin, hipMemcpyHostToDevice, st) != hipSuccess)
                 return fail(MAGE_EDEVICE);
-            const uint32_t newest = (R.first + R.count - 1) % NK;
-            if (hipMemcpyAsync(dposes + 12ull * f, &R.pose[12 * newest], 96, hipMemcpyHostToDevice, st) != hipSuccess ||
-                hipMemcpyAsync(&b.ctl->halt, R.zero.data(), 4, hipMemcpyHostToDevice, st) != hipSuccess)
+            const uint32_t newest = (hc.kf_first + hc.kf_count - 1) % NK;
+            if (hipMemcpyAsync(blk.poses + 12ull * f, &R.v.kf_pose[12 * newest], 96, hipMemcpyHostToDevice, st) !=
+                    hipSuccess ||
+                hipMemcpyAsync(&b.ctl->halt, zero.data(), 4, hipMemcpyHostToDevice, st) != hipSuccess)
                 return fail(MAGE_EDEVICE);
             prof.mark("write-back");
             prof.flush();
@@ -1321,11 +772,11 @@ extern "C" mage_status mage_track_sequence_device(const mage_keypoint* d_kp, con
     }
     if (hipGetLastError() != hipSuccess) return fail(MAGE_EDEVICE);
     uint32_t rst = 0, lst = 0;
-    if (hipMemcpyAsync(poses, dposes, 96ull * frames, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(matches, dmt, 4ull * frames, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(inliers, dil, 4ull * frames, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(keyframe, dkf, frames, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(&rst, rstatus, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+    if (hipMemcpyAsync(poses, blk.poses, 96ull * frames, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(matches, blk.matches, 4ull * frames, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(inliers, blk.inliers, 4ull * frames, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(keyframe, blk.keyframe, frames, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(&rst, blk.rstatus, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipMemcpyAsync(&lst, b.lm_status, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess)
         return fail(MAGE_EDEVICE);

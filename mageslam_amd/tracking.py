@@ -216,22 +216,13 @@ def make_keyframe(fid: int, pose: Pose, kp, desc, K, plane_z: float, s: "Tracker
     1.f / length), d = |centre - point|, dmax / dmin = d x the octave's ComputeDMax / DMin factor."""
     factor = depth_noise_factor(fid, len(kp), s.map_point_depth_noise) if s.map_point_depth_noise else None
     pts = backproject_to_plane(kp, pose, K, plane_z, factor)
-    C = world_position_f32(pose)
-    v = (pts - C).astype(np.float32)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        d = np.sqrt(_dot3(v, v)).astype(np.float32)
-        n1 = np.where(d[:, None] == 0, v, v * (np.float32(1) / d)[:, None]).astype(np.float32)
-        d2 = np.sqrt(_dot3(n1, n1)).astype(np.float32)
-        mvd = np.where(d2[:, None] == 0, n1, n1 * (np.float32(1) / d2)[:, None]).astype(np.float32)
-    delta = (C - pts).astype(np.float32)
-    dist = np.sqrt((delta[:, 0] * delta[:, 0] + delta[:, 1] * delta[:, 1]) + delta[:, 2] * delta[:, 2]).astype(np.float32)
-    fmax, fmin = s.octave_factors()
-    octv = np.asarray(kp["octave"], np.int64)
     n = len(kp)
-    return Keyframe(pose, kp, desc, pts, fid, mvd, (dist * fmin[octv]).astype(np.float32),
-                    (dist * fmax[octv]).astype(np.float32), refine=np.zeros(n, np.uint32),
-                    own_alive=np.ones(n, bool), assoc_owner=np.zeros(0, np.int64), assoc_idx=np.zeros(0, np.int64),
-                    assoc_uv=np.zeros((0, 2), np.float32), assoc_alive=np.zeros(0, bool))
+    kf = Keyframe(pose, kp, desc, pts, fid, np.zeros((n, 3), np.float32), np.zeros(n, np.float32),
+                  np.zeros(n, np.float32), refine=np.zeros(n, np.uint32),
+                  own_alive=np.ones(n, bool), assoc_owner=np.zeros(0, np.int64), assoc_idx=np.zeros(0, np.int64),
+                  assoc_uv=np.zeros((0, 2), np.float32), assoc_alive=np.zeros(0, bool))
+    point_attributes(kf, s, np.arange(n))
+    return kf
 
 
 def point_attributes(kf: Keyframe, s: "TrackerSettings", idx: np.ndarray) -> None:
@@ -248,7 +239,7 @@ def point_attributes(kf: Keyframe, s: "TrackerSettings", idx: np.ndarray) -> Non
     delta = (C - pts).astype(np.float32)
     dist = np.sqrt((delta[:, 0] * delta[:, 0] + delta[:, 1] * delta[:, 1]) + delta[:, 2] * delta[:, 2]).astype(np.float32)
     fmax, fmin = s.octave_factors()
-    octv = np.asarray(kf.kp["octave"][idx], np.int64)
+    octv = np.clip(np.asarray(kf.kp["octave"][idx], np.int64), 0, 7)  # the tables' range, as the native loops clamp
     kf.dmin[idx] = (dist * fmin[octv]).astype(np.float32)
     kf.dmax[idx] = (dist * fmax[octv]).astype(np.float32)
 

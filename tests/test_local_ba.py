@@ -20,8 +20,7 @@ def _kf(fid, n, t):
     return k
 
 
-def test_window_structure():
-    s = tracking.TrackerSettings(ba_free_keyframes=2)  # the newest-N rule
+def _structure_ring():
     k0, k1, k2 = _kf(0, 3, 0.0), _kf(10, 2, 0.1), _kf(20, 2, 0.2)
     # k1 observes k0's point 1 and 2 (the second association dead); k2 observes k1's point 0
     k1.assoc_owner, k1.assoc_idx = np.array([0, 0]), np.array([1, 2])
@@ -30,6 +29,12 @@ def test_window_structure():
     k2.assoc_uv, k2.assoc_alive = np.float32([[5, 6], [7, 8]]), np.array([True, True])
     k0.refine[1] = 2
     k1.own_alive[1] = False
+    return [k0, k1, k2]
+
+
+def test_window_structure():
+    s = tracking.TrackerSettings(ba_free_keyframes=2)  # the newest-N rule
+    k0, k1, k2 = _structure_ring()
     w, _ = tracking.build_ba_window([k0, k1, k2], (900.0, 900.0, 640.0, 360.0), s)
     # points a free keyframe observes: k0's point 1 (by k1), k1's point 0 (own + k2), k2's points
     assert w.point_src == [(0, 1), (1, 0), (2, 0), (2, 1)]
