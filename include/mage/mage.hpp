@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <array>
 #include <cstdint>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -440,6 +441,191 @@ inline std::vector<MapPointKeyframeAssociations> NewMapPointsCreation(
     }
     return out;
 }
+
+// StereoMapInitializationSettings (MageSettings.h:135-147) with its OrbMatcherSettings and
+// BundleAdjustSettings bags (:36-52).
+struct StereoMapInitializationSettings {
+    unsigned MinInitMapPoints{15}, MinFeatureMatches{40};
+    float MaxOutlierError{2.5f};
+    float MaxEpipolarError{5.5f};
+    float MinAcceptedDistanceRatio{2.0f};
+    float InitializationTetherStrength{50.0f};
+    float MaxPoseContributionZ{0.10f};
+    float AmountBACanChangePose{1.65f};
+    float MaxDepthMeters{2.3f};
+    struct {
+        int MaxHammingDistance{30}, MinHammingDifference{1};
+    } OrbMatcherSettings;
+    struct {
+        unsigned NumSteps{1}, NumStepsPerRun{1}, MinSteps{1};
+        float HuberWidth{1.8f}, HuberWidthScale{0.95f}, MaxOutlierError{7.25f}, MaxOutlierErrorScaleFactor{0.95f};
+        float MinMeanSquareError{0.25f}, DistanceTetherWeight{50.f}, LowConnectivityIterationsScale{1.5f};
+    } BundleAdjustSettings;
+
+    mage_stereo_init_settings ToC() const
+    {
+        mage_stereo_init_settings s{};
+        s.struct_size = (uint32_t)sizeof(s);
+        s.min_init_map_points = MinInitMapPoints;
+        s.min_feature_matches = MinFeatureMatches;
+        s.max_outlier_error = MaxOutlierError;
+        s.max_epipolar_error = MaxEpipolarError;
+        s.min_accepted_distance_ratio = MinAcceptedDistanceRatio;
+        s.initialization_tether_strength = InitializationTetherStrength;
+        s.max_pose_contribution_z = MaxPoseContributionZ;
+        s.amount_ba_can_change_pose = AmountBACanChangePose;
+        s.max_depth_meters = MaxDepthMeters;
+        s.max_hamming_distance = OrbMatcherSettings.MaxHammingDistance;
+        s.min_hamming_difference = OrbMatcherSettings.MinHammingDifference;
+        s.ba_num_steps = BundleAdjustSettings.NumSteps;
+        s.ba_num_steps_per_run = BundleAdjustSettings.NumStepsPerRun;
+        s.ba_min_steps = BundleAdjustSettings.MinSteps;
+        s.ba_huber_width = BundleAdjustSettings.HuberWidth;
+        s.ba_huber_width_scale = BundleAdjustSettings.HuberWidthScale;
+        s.ba_max_outlier_error = BundleAdjustSettings.MaxOutlierError;
+        s.ba_max_outlier_error_scale_factor = BundleAdjustSettings.MaxOutlierErrorScaleFactor;
+        s.ba_min_mean_square_error = BundleAdjustSettings.MinMeanSquareError;
+        s.ba_distance_tether_weight = BundleAdjustSettings.DistanceTetherWeight;
+        s.ba_low_connectivity_iterations_scale = BundleAdjustSettings.LowConnectivityIterationsScale;
+        return s;
+    }
+};
+
+using StereoPoint = mage_stereo_point;
+
+// What StereoMapInit::Initialize has when InitializeWithFrames returns (StereoMapInit.cpp:47-88,
+// :104-159): frame 0's crop mask, Match's result, one MAGE_ST_* verdict per match, the accepted
+// matches with their points in match order (the two keyframe builders' associations are QueryIdx
+// in frame 0 and TrainIdx in frame 1, :83-87) and the arrays BundleAdjustInitializationData gives
+// the bundler (BundlerLib::SetMapPoint / SetObservation order).
+struct StereoTriangulation {
+    std::vector<bool> Frame0Mask;
+    std::vector<DMatch> Matches;
+    std::vector<uint8_t> Verdicts;
+    std::vector<StereoPoint> Points;
+    std::vector<float> BundlePoints, BundleObservations, BundleInformation;
+    std::vector<uint32_t> BundleCameras, BundleMapPoints;
+};
+
+// The stretch of StereoMapInit::Initialize between the crop (:100) and the map-point count test
+// (:161) for one pair: frame 0's keypoints masked to `crop` {x, y, width, height}, the masked frame 0
+// matched against frame 1, every match through MapInitialization::TriangulatePoints with frame 0
+// as the reference frame.  Descriptors are n x 32 bytes per frame; with `matches` given they are not
+// read and no matcher runs.  device < 0 runs the CPU backend, which needs `matches`.
+inline StereoTriangulation TriangulateStereoPair(const StereoMapInitializationSettings& settings,
+                                                 const KeyframeView& frame0, const uint8_t* frame0Descriptors,
+                                                 const KeyframeView& frame1, const uint8_t* frame1Descriptors,
+                                                 const std::array<int32_t, 4>& crop,
+                                                 const std::vector<DMatch>* matches = nullptr, int device = 0)
+{
+    if (!matches && (device < 0 || !frame0Descriptors || !frame1Descriptors))
+        throw std::invalid_argument("without matches both descriptor sets and a device are needed");
+    const mage_stereo_init_settings s = settings.ToC();
+    const uint32_t n0 = (uint32_t)frame0.KeyPoints->size(), n1 = (uint32_t)frame1.KeyPoints->size();
+    float pos[6], rot[18], intr[8];
+    for (int f = 0; f < 2; f++) {
+        const KeyframeView& v = f ? frame1 : frame0;
+        std::copy(v.Position.begin(), v.Position.end(), pos + 3 * f);
+        std::copy(v.Rotation.begin(), v.Rotation.end(), rot + 9 * f);
+        std::copy(v.Intrinsics.begin(), v.Intrinsics.end(), intr + 4 * f);
+    }
+    StereoTriangulation r;
+    if (matches) r.Matches = *matches;
+    uint32_t nm = (uint32_t)r.Matches.size();
+    const uint32_t cap = std::max<uint32_t>(matches ? nm : n0, 1);
+    r.Matches.resize(cap);
+    std::vector<uint8_t> mask(std::max<uint32_t>(n0, 1));
+    r.Verdicts.assign(cap, 0xFF);
+    r.Points.resize(cap);
+    r.BundlePoints.resize(3 * (size_t)cap);
+    r.BundleObservations.resize(4 * (size_t)cap);
+    r.BundleInformation.resize(2 * (size_t)cap);
+    r.BundleCameras.resize(2 * (size_t)cap);
+    r.BundleMapPoints.resize(2 * (size_t)cap);
+    uint32_t masked = 0, n = 0, status = 0;
+    if (device < 0)
+        check(mage_stereo_init_triangulate_host(&s, pos, rot, intr, crop.data(), frame0.KeyPoints->data(), n0,
+                                                frame1.KeyPoints->data(), n1, r.Matches.data(), nm, mask.data(), &masked,
+                                                r.Verdicts.data(), r.Points.data(), cap, &n, r.BundlePoints.data(),
+                                                r.BundleObservations.data(), r.BundleCameras.data(),
+                                                r.BundleMapPoints.data(), r.BundleInformation.data(), &status));
+    else
+        check(mage_stereo_init_triangulate(&s, pos, rot, intr, crop.data(), frame0.KeyPoints->data(),
+                                           matches ? nullptr : frame0Descriptors, n0, frame1.KeyPoints->data(),
+                                           matches ? nullptr : frame1Descriptors, n1, r.Matches.data(), cap, &nm,
+                                           mask.data(), &masked, r.Verdicts.data(), r.Points.data(), cap, &n,
+                                           r.BundlePoints.data(), r.BundleObservations.data(), r.BundleCameras.data(),
+                                           r.BundleMapPoints.data(), r.BundleInformation.data(), &status, device));
+    if (status & MAGE_ST_STATUS_OVER_LIMIT) throw Error(MAGE_EUNSUPPORTED, "more than 4096 keypoints in a frame");
+    r.Frame0Mask.assign(mask.begin(), mask.begin() + n0);
+    r.Matches.resize(nm);
+    r.Verdicts.resize(nm);
+    r.Points.resize(n);
+    r.BundlePoints.resize(3 * (size_t)n);
+    r.BundleObservations.resize(4 * (size_t)n);
+    r.BundleInformation.resize(2 * (size_t)n);
+    r.BundleCameras.resize(2 * (size_t)n);
+    r.BundleMapPoints.resize(2 * (size_t)n);
+    return r;
+}
+
+// What StereoMapInit::Initialize reads of an AnalyzedImage: the undistorted calibration and size
+// (the extrinsics field is not read), the keypoints and their 32-byte descriptors.
+struct StereoFrame {
+    mage_camera_config Camera;
+    const std::vector<KeyPoint>* KeyPoints;
+    const uint8_t* Descriptors;
+};
+
+// The reference's InitializationData for a stereo pair: two keyframe builders — frame 0 at the
+// identity, frame 1 at Frame1Position / Frame1Rotation (view-space t, column-major R) — and the
+// map points; MapPoints[i] is associated with keypoint query_idx of frame 0 and train_idx of frame 1.
+struct InitializationData {
+    std::array<float, 3> Frame1Position;
+    std::array<float, 9> Frame1Rotation;
+    std::vector<StereoPoint> MapPoints;
+};
+
+// StereoMapInit (Stereo/StereoMapInit.h:23-35) over mage_stereo_map_init.
+class StereoMapInit {
+public:
+    explicit StereoMapInit(const StereoMapInitializationSettings& settings, int device = 0)
+        : m_settings(settings.ToC()), m_device(device)
+    {
+    }
+
+    // Initialize (Stereo/StereoMapInit.cpp:97-194): std::nullopt where the reference returns
+    // boost::none; LastResult() then says why (MAGE_STEREO_INIT_*).
+    std::optional<InitializationData> Initialize(const StereoFrame& frame0, const StereoFrame& frame1,
+                                                 const std::array<float, 16>& frame0ToFrame1)
+    {
+        const uint32_t n0 = (uint32_t)frame0.KeyPoints->size(), n1 = (uint32_t)frame1.KeyPoints->size();
+        const size_t cap = std::max<size_t>(n0, 1);
+        const size_t runs = m_settings.ba_num_steps / std::max(m_settings.ba_num_steps_per_run, 1u) + 2;
+        std::vector<uint8_t> mask(cap), verdict(cap);
+        std::vector<DMatch> matches(cap);
+        std::vector<StereoPoint> points(cap);
+        std::vector<uint32_t> outliers(2 * cap * runs);
+        m_last = mage_stereo_map_init_result{};
+        check(mage_stereo_map_init(&m_settings, frame0ToFrame1.data(), &frame0.Camera, &frame1.Camera,
+                                   frame0.KeyPoints->data(), frame0.Descriptors, n0, frame1.KeyPoints->data(),
+                                   frame1.Descriptors, n1, &m_last, mask.data(), matches.data(), verdict.data(),
+                                   points.data(), outliers.data(), m_device));
+        if (m_last.code != MAGE_STEREO_INIT_OK) return std::nullopt;
+        InitializationData d;
+        std::copy(m_last.frame1_pos3, m_last.frame1_pos3 + 3, d.Frame1Position.begin());
+        std::copy(m_last.frame1_r9, m_last.frame1_r9 + 9, d.Frame1Rotation.begin());
+        d.MapPoints.assign(points.begin(), points.begin() + m_last.n_points);
+        return d;
+    }
+
+    const mage_stereo_map_init_result& LastResult() const { return m_last; }
+
+private:
+    mage_stereo_init_settings m_settings;
+    int m_device;
+    mage_stereo_map_init_result m_last{};
+};
 
 struct BundlerParameters {
     bool ArePointsFixed{false};

@@ -234,6 +234,16 @@ mage_status mage_scale_for_camera_configuration(const mage_camera_config* source
                                                 float max_depth_meters, int32_t crop_xywh[4], float* scale,
                                                 mage_camera_config* prepared, int32_t* ok);
 
+/* CalculateOverlapCropSourceInTarget (MageUtil.cpp:13-58) from the matrix itself, the inner part of
+ * the geometry above: the cv::Rect, in the target frame, of the source frame's corners at
+ * depth_meters.  StereoMapInit::Initialize (Stereo/StereoMapInit.cpp:100) calls it with
+ * target_to_source = frame0ToFrame1 (cv::Matx44f, row-major), target = frame 0's camera and source =
+ * frame 1's to get the crop that masks frame 0's keypoints (mage_stereo_init_triangulate*'s crop).
+ * The cameras' extrinsics fields are not read.  Host only. */
+mage_status mage_overlap_crop_source_in_target(const float target_to_source[16], const mage_camera_config* target,
+                                               const mage_camera_config* source, float depth_meters,
+                                               int32_t crop_xywh[4]);
+
 /* The whole call on a device image: the geometry above, then the source->width x source->height
  * image at d_src (src_stride) resized with INTER_LINEAR into d_dst (dst_stride; prepared->height
  * rows of prepared->width bytes; dst_capacity bytes available), or copied when scale == 1.
@@ -583,6 +593,207 @@ mage_status mage_new_points_associate_batch_device(const mage_new_points_setting
                                                    const uint32_t* d_n_kf_kp, const int32_t* d_kf_slot,
                                                    mage_new_point_assoc* d_assoc, uint8_t* d_verdict,
                                                    uint32_t* d_status, mage_stream stream);
+
+/* ------------------------------------------------------------------------------------------ */
+/* Stereo map initialisation — the device stage of StereoMapInit::Initialize                   */
+/* (Core/.../Source/Stereo/StereoMapInit.cpp:97-194)                                           */
+/* ------------------------------------------------------------------------------------------ */
+
+/* StereoMapInitializationSettings (MageSettings.h:135-147) in the reference's order: its nine
+ * scalars, then its OrbMatcherSettings bag (:36-39) and its BundleAdjustSettings bag (:41-52).
+ * struct_size must be sizeof(mage_stereo_init_settings); anything else is MAGE_EINVAL.  The device
+ * stage reads max_epipolar_error, min_accepted_distance_ratio and the matcher's two; the others
+ * belong to Initialize's host part (match and point counts, tether, bundle adjustment, validation). */
+typedef struct mage_stereo_init_settings {
+    uint32_t struct_size;
+    uint32_t min_init_map_points;          /* MinInitMapPoints 15 */
+    uint32_t min_feature_matches;          /* MinFeatureMatches 40 */
+    float max_outlier_error;               /* MaxOutlierError 2.5 (Initialize never reads it) */
+    float max_epipolar_error;              /* MaxEpipolarError 5.5 (pixels) */
+    float min_accepted_distance_ratio;     /* MinAcceptedDistanceRatio 2.0 */
+    float initialization_tether_strength;  /* InitializationTetherStrength 50 */
+    float max_pose_contribution_z;         /* MaxPoseContributionZ 0.10 */
+    float amount_ba_can_change_pose;       /* AmountBACanChangePose 1.65 */
+    float max_depth_meters;                /* MaxDepthMeters 2.3 */
+    int32_t max_hamming_distance;          /* OrbMatcherSettings.MaxHammingDistance 30, in [-1, 256] */
+    int32_t min_hamming_difference;        /* OrbMatcherSettings.MinHammingDifference 1 */
+    uint32_t ba_num_steps;                 /* BundleAdjustSettings.NumSteps 1 */
+    uint32_t ba_num_steps_per_run;         /* NumStepsPerRun 1 */
+    uint32_t ba_min_steps;                 /* MinSteps 1 */
+    float ba_huber_width;                  /* HuberWidth 1.8 */
+    float ba_huber_width_scale;            /* HuberWidthScale 0.95 */
+    float ba_max_outlier_error;            /* MaxOutlierError 7.25 */
+    float ba_max_outlier_error_scale_factor; /* MaxOutlierErrorScaleFactor 0.95 */
+    float ba_min_mean_square_error;        /* MinMeanSquareError 0.25 */
+    float ba_distance_tether_weight;       /* DistanceTetherWeight 50 */
+    float ba_low_connectivity_iterations_scale; /* LowConnectivityIterationsScale 1.5 */
+} mage_stereo_init_settings;
+
+/* One accepted match, as TriangulatePoints' initial3DPoints.emplace_back(match, point) keeps it
+ * (MapInitialization.cpp:984): the DMatch's indices and distance, the triangulated point, and
+ * whether TriangulatePointWorldSpace took its near-parallel branch (D < 0.00001f,
+ * Triangulation.cpp:24-60).  28 bytes. */
+typedef struct mage_stereo_point {
+    int32_t query_idx, train_idx; /* frame 0's keypoint, frame 1's keypoint */
+    float distance;
+    float position[3];
+    uint32_t near_parallel;
+} mage_stereo_point;
+
+/* Verdict of a match: TriangulatePoints' first reason to drop it, in its order. */
+#define MAGE_ST_ACCEPTED 0
+#define MAGE_ST_EPIPOLAR 1       /* both epipolar distances sum over 2 * MaxEpipolarError (:945-950) */
+#define MAGE_ST_BEHIND 2         /* VerifyProjectInFront of frame 0, then frame 1 (:956-960) */
+#define MAGE_ST_DISTANCE_RATIO 3 /* |X - C0| / |C0 - C1| < MinAcceptedDistanceRatio (:966-974) */
+#define MAGE_ST_OCTAVE 4         /* the two keypoints' octaves differ (:977-980) */
+#define MAGE_ST_BAD_INDEX 5      /* queryIdx / trainIdx is not a keypoint: nothing read */
+
+/* Bits of a pair's status word. */
+#define MAGE_ST_STATUS_OVER_LIMIT 1u /* a frame has more than 4096 keypoints, or more than its pitch */
+#define MAGE_ST_STATUS_OVER_CAP 2u   /* more accepted matches than `cap` (the count reports cap) */
+
+/* Initialize's device stage for `pairs` stereo pairs, three launches on `stream` with no host step
+ * between them:
+ *   a. CreateFilteredDescriptorMask(-1, crop, frame0) (StereoMapInit.cpp:28-45, :104-105): frame
+ *      0's mask byte per keypoint from IsWithinArea(kp.pt, crop) (Utils/cv.h:421-427: x in
+ *      [crop.x, crop.x + width), y in [crop.y, crop.y + height] — the bottom edge is inside), the
+ *      true count in d_n_masked[pair]; frame 1 is unmasked (:107-108).  The masked descriptors are
+ *      packed in keypoint order, as Match packs descriptorMatrixA (FeatureMatcher.cpp:84-108).
+ *   b. Match (:112) by mage_hamming_match_batch_device over the packed frame 0 (A) and frame 1 (B)
+ *      with the settings' MaxHammingDistance / MinHammingDifference; queryIdx is mapped back to
+ *      frame 0's keypoint index, so d_matches / d_n_matches hold Match's result (ascending
+ *      queryIdx; a count over match_cap means only match_cap were kept).
+ *   c. MapInitialization::TriangulatePoints (Tracking/MapInitialization.cpp:911-986) over the
+ *      matches in order, frame 0 the reference frame and frame 1 the current frame:
+ *      d_verdict[pair * match_cap + m] = MAGE_ST_*; the accepted matches in match order at
+ *      d_out + pair * cap, their count (at most cap) in d_n_out[pair]; and the bundle adjustment's
+ *      inputs as BundleAdjustInitializationData enumerates them (:1099-1110, frame-major) for the
+ *      n = d_n_out[pair] points: d_ba_points + pair * 3 cap (n x 3), and 2n observations at
+ *      pair * 2 cap of d_ba_uv (2 floats each), d_ba_cam, d_ba_pt and d_ba_info — observation i
+ *      is point i in frame 0 (cam 0, frame 0's keypoint position), observation n + i point i in
+ *      frame 1; info = MapPointRefinementConfidence(1) (init points are created with refinement
+ *      count 1, StereoMapInit.cpp:77).  These are mage_ba_set_points / mage_ba_set_observations'
+ *      arguments.
+ * Per pair: poses as mage_ba_set_cameras takes them, frame 0 then frame 1 (d_pos3 6 floats, d_r9
+ * 18, d_intr4 8 = {cx, cy, fx, fy} twice); d_crop the cv::Rect {x, y, width, height} of
+ * CalculateOverlapCropSourceInTarget (:100); frame f's keypoints and 32-byte descriptors pitch0 /
+ * pitch1 entries per pair, counts d_n0 / d_n1.  d_mask0: pitch0 bytes per pair.  d_scratch: pairs
+ * x pitch0 x 36 bytes, 16-byte aligned like the descriptors.
+ * d_desc0 == NULL skips (b): d_matches / d_n_matches are then inputs (queryIdx = frame 0's
+ * keypoint), read as above, and d_desc1 / d_scratch are not used.
+ * d_status[pair] is written (not ORed): MAGE_ST_STATUS_OVER_LIMIT for a pair with a keypoint count
+ * over 4096 or over its pitch — that pair reports 0 masked keypoints, 0 matches from (b) and 0
+ * points, and its mask and verdict bytes are left untouched; MAGE_ST_STATUS_OVER_CAP when more
+ * matches were accepted than cap.  Nothing is written past a pair's counts: mask bytes past
+ * d_n0[pair], verdicts past min(d_n_matches[pair], match_cap), records and points past
+ * d_n_out[pair], observations past 2 d_n_out[pair].  The other pairs are unaffected. */
+mage_status mage_stereo_init_triangulate_batch_device(
+    const mage_stereo_init_settings* settings, uint32_t pairs, const float* d_pos3, const float* d_r9,
+    const float* d_intr4, const int32_t* d_crop, const mage_keypoint* d_kp0, const uint8_t* d_desc0, int64_t pitch0,
+    const uint32_t* d_n0, const mage_keypoint* d_kp1, const uint8_t* d_desc1, int64_t pitch1, const uint32_t* d_n1,
+    uint8_t* d_mask0, uint32_t* d_n_masked, mage_dmatch* d_matches, uint32_t match_cap, uint32_t* d_n_matches,
+    uint8_t* d_verdict, mage_stereo_point* d_out, uint32_t cap, uint32_t* d_n_out, float* d_ba_points, float* d_ba_uv,
+    uint32_t* d_ba_cam, uint32_t* d_ba_pt, float* d_ba_info, uint32_t* d_status, void* d_scratch, mage_stream stream);
+
+/* One pair, host buffers, synchronous, runs on `device`: arrays as one pair of the batched form.
+ * With desc0 / desc1 (n x 32 bytes) the matcher runs and `matches` (match_cap records, at least
+ * one) and *n_matches are outputs — Match's result, queryIdx = frame 0's keypoint; a result
+ * longer than match_cap is cut to its first match_cap.  With desc0 == NULL the first *n_matches
+ * records of `matches` are the input.  verdict: one byte per match; out and ba_* sized for cap
+ * points (cap == 0: every accepted match is over the capacity).  More than 4096 keypoints in a
+ * frame sets MAGE_ST_STATUS_OVER_LIMIT in *status and writes nothing else. */
+mage_status mage_stereo_init_triangulate(const mage_stereo_init_settings* settings, const float* pos3, const float* r9,
+                                         const float* intr4, const int32_t crop_xywh[4], const mage_keypoint* kp0,
+                                         const uint8_t* desc0, uint32_t n0, const mage_keypoint* kp1,
+                                         const uint8_t* desc1, uint32_t n1, mage_dmatch* matches, uint32_t match_cap,
+                                         uint32_t* n_matches, uint8_t* mask0, uint32_t* n_masked, uint8_t* verdict,
+                                         mage_stereo_point* out, uint32_t cap, uint32_t* n_out, float* ba_points,
+                                         float* ba_uv, uint32_t* ba_cam, uint32_t* ba_pt, float* ba_info,
+                                         uint32_t* status, int device);
+
+/* Stages (a) and (c) for one pair in plain C++ on the calling thread, the matches given (queryIdx
+ * = frame 0's keypoint): the reference's sequential loops over the same per-match arithmetic, the
+ * CPU backend, bit-identical to the kernels.  Arrays as one pair of the batched form, ba_* sized
+ * for cap points.  No GPU. */
+mage_status mage_stereo_init_triangulate_host(const mage_stereo_init_settings* settings, const float* pos3,
+                                              const float* r9, const float* intr4, const int32_t crop_xywh[4],
+                                              const mage_keypoint* kp0, uint32_t n0, const mage_keypoint* kp1,
+                                              uint32_t n1, const mage_dmatch* matches, uint32_t n_matches,
+                                              uint8_t* mask0, uint32_t* n_masked, uint8_t* verdict,
+                                              mage_stereo_point* out, uint32_t cap, uint32_t* n_out, float* ba_points,
+                                              float* ba_uv, uint32_t* ba_cam, uint32_t* ba_pt, float* ba_info,
+                                              uint32_t* status);
+
+/* What StereoMapInit::Initialize returns: boost::none for four reasons, or the InitializationData. */
+#define MAGE_STEREO_INIT_OK 0
+#define MAGE_STEREO_INIT_ZERO_DISPLACEMENT 1 /* |translation of frame0ToFrame1| < 0.00001 (:139) */
+#define MAGE_STEREO_INIT_FEW_MATCHES 2       /* fewer than MinFeatureMatches matches (:151) */
+#define MAGE_STEREO_INIT_FEW_POINTS 3        /* fewer than MinInitMapPoints accepted matches (:161) */
+#define MAGE_STEREO_INIT_FAILED_VALIDATION 4 /* ValidateInitializationData (:183) */
+
+typedef struct mage_stereo_map_init_result {
+    int32_t code;          /* MAGE_STEREO_INIT_* */
+    int32_t crop[4];       /* frame0CropRect {x, y, width, height} (:100) */
+    uint32_t n_masked;     /* numFilteredDescriptorsFrame0 (:105) */
+    uint32_t n_matches;    /* numMatches (:112) */
+    uint32_t n_verdicts;   /* n_matches once TriangulatePoints ran (code >= FEW_POINTS or OK), else 0 */
+    float frame1_pos3[3];  /* frame 1's pose, view-space t and column-major R as mage_ba_set_cameras */
+    float frame1_r9[9];    /*   takes them: after the bundle adjustment, else as normalised, else identity */
+    uint32_t n_points;     /* surviving map points */
+    uint32_t n_ba_outliers;
+    uint32_t ba_runs;      /* StepBundleAdjustment calls (RunBundleAdjustment's return value) */
+} mage_stereo_map_init_result;
+
+/* StereoMapInit::Initialize (Stereo/StereoMapInit.cpp:97-194) for one pair of analysed frames, host
+ * buffers, synchronous, on `device`, in the reference's order:
+ *   1. the crop (:100, mage_overlap_crop_source_in_target with MaxDepthMeters), frame 0's mask and the
+ *      two-way Match (:104-114) — on the GPU, with step 4 behind them in the same chain;
+ *   2. frame0ToFrame1's translation normalised to length 1, in float (:135-148); a length below
+ *      0.00001 is ZERO_DISPLACEMENT (reported even when there are too few matches as well);
+ *   3. fewer than MinFeatureMatches matches is FEW_MATCHES;
+ *   4. InitializeWithFrames (:47-88): frame 0 at the identity, frame 1 at Pose{normalized.inv()} — the
+ *      LU inverse is the pose's inverse view matrix and its view matrix is Invert() of that
+ *      (Data/Pose.cpp:31-36) — and TriangulatePoints over the matches;
+ *   5. fewer than MinInitMapPoints accepted matches is FEW_POINTS;
+ *   6. AddExtrinsicTether(frame 0, InitializationTetherStrength) (:168, KeyframeBuilder.h:38-48) and
+ *      BundleAdjustInitializationData (MapInitialization.cpp:1096-1226): camera 0 fixed, points free,
+ *      RunBundleAdjustment's schedule with the NoOpScheduler (BundleAdjust.cpp:293-346: runs of
+ *      NumStepsPerRun steps at HuberWidth, the outlier bound starting at BundleAdjustSettings.
+ *      MaxOutlierError and multiplied by MaxOutlierErrorScaleFactor^2 after every run, until NumSteps
+ *      steps or a residual <= MinMeanSquareError after MinSteps), the tether through
+ *      mage_ba_set_tethers(MAGE_TETHER_TRANSFORM) after BuildDataForG2O's second inversion
+ *      (BundleAdjust.cpp:177-192); frame 1's pose from GetPose, the points from GetPoint; every
+ *      outlier association removed and every point left with fewer than 2 removed by swap-with-back
+ *      (:1166-1222);
+ *   7. ValidateInitializationData (:1228-1268): the point count, |normalised world z| of frame 1 over
+ *      MaxPoseContributionZ, its distance from the origin outside [1 / AmountBACanChangePose,
+ *      AmountBACanChangePose] -> FAILED_VALIDATION.
+ * A failure is a normal return (MAGE_OK with the code set).  The cameras are frame 0's and frame 1's
+ * undistorted calibrations and sizes (extrinsics not read).  Outputs, each with room for n0 entries
+ * (ba_outliers: 2 n0 per bundle adjustment run): mask0 and matches[0 .. n_matches) always; verdict[0
+ * .. n_verdicts) from step 4 on; points[0 .. n_points) — the surviving points in the reference's
+ * order after its swaps, position from the bundle adjustment, query_idx / train_idx the two
+ * keyframes' associations — and ba_outliers[0 .. n_ba_outliers), observation indices over the runs
+ * (observation o < n is accepted match o in frame 0, o >= n match o - n in frame 1), from step 6
+ * on.  More than 4096 keypoints in a frame is MAGE_EUNSUPPORTED. */
+mage_status mage_stereo_map_init(const mage_stereo_init_settings* settings, const float frame0_to_frame1[16],
+                                 const mage_camera_config* camera0, const mage_camera_config* camera1,
+                                 const mage_keypoint* kp0, const uint8_t* desc0, uint32_t n0, const mage_keypoint* kp1,
+                                 const uint8_t* desc1, uint32_t n1, mage_stereo_map_init_result* result, uint8_t* mask0,
+                                 mage_dmatch* matches, uint8_t* verdict, mage_stereo_point* points,
+                                 uint32_t* ba_outliers, int device);
+
+/* Debug view of mage_stereo_map_init's host arithmetic, no device; each part runs when its first
+ * pointer is given.  frame0_to_frame1: step 2 and 4's scalars (the zero-displacement flag, the
+ * normalised matrix, frame 1's pose) and the 7 tether parameters of step 6.  order: the culling of
+ * step 6 for n_points accepted matches and the given outlier observation indices -> the surviving
+ * points' indices in output order, *n_left of them.  valid: step 7 for frame 1's pose ba_pos3 /
+ * ba_r9 and the surviving count (n_points when `order` is not given). */
+mage_status mage_debug_stereo_init_host(const mage_stereo_init_settings* settings, const float frame0_to_frame1[16],
+                                        int32_t* zero_displacement, float normalized[16], float pos3[3], float r9[9],
+                                        float tether7[7], uint32_t n_points, const uint32_t* outliers,
+                                        uint32_t n_outliers, uint32_t* order, uint32_t* n_left, const float* ba_pos3,
+                                        const float* ba_r9, int32_t* valid);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Local bundle adjustment — replaces BundlerLib (Dependencies/BundlerLib/Include/BundlerLib.h) */

@@ -28,7 +28,7 @@ EXPORTS = [
     "mage_undistort_keypoints", "mage_undistort_keypoints_batch_device",
     "mage_undistorter_create", "mage_undistorter_destroy", "mage_undistorter_get_maps", "mage_undistort_image",
     "mage_undistort_image_batch_device", "mage_resize_linear_device", "mage_scale_for_camera_configuration",
-    "mage_scale_image_for_camera_configuration_device",
+    "mage_scale_image_for_camera_configuration_device", "mage_overlap_crop_source_in_target",
     "mage_hamming_distance", "mage_hamming_match", "mage_hamming_match_batch_device",
     "mage_radius_match", "mage_radius_match_batch_device", "mage_local_map_match",
     "mage_bow_create", "mage_bow_destroy", "mage_bow_train", "mage_bow_train_kmedoid", "mage_bow_get_tree", "mage_bow_find_leaves", "mage_bow_find_leaves_device",
@@ -40,6 +40,8 @@ EXPORTS = [
     "mage_track_sequence", "mage_track_sequence_device",
     "mage_new_map_points", "mage_new_map_points_host", "mage_new_map_points_batch_device",
     "mage_new_points_associate", "mage_new_points_associate_host", "mage_new_points_associate_batch_device",
+    "mage_stereo_map_init", "mage_debug_stereo_init_host",
+    "mage_stereo_init_triangulate", "mage_stereo_init_triangulate_batch_device", "mage_stereo_init_triangulate_host",
 ]
 
 
@@ -135,6 +137,31 @@ class NewPointsAssocSettingsC(C.Structure):
         return cls(struct_size=C.sizeof(cls), **kw)
 
 
+class StereoInitSettingsC(C.Structure):
+    """mage_stereo_init_settings (include/mage_hot.h); struct_size is filled in by make()."""
+    _fields_ = [("struct_size", C.c_uint32), ("min_init_map_points", C.c_uint32), ("min_feature_matches", C.c_uint32),
+                ("max_outlier_error", C.c_float), ("max_epipolar_error", C.c_float),
+                ("min_accepted_distance_ratio", C.c_float), ("initialization_tether_strength", C.c_float),
+                ("max_pose_contribution_z", C.c_float), ("amount_ba_can_change_pose", C.c_float),
+                ("max_depth_meters", C.c_float), ("max_hamming_distance", C.c_int32),
+                ("min_hamming_difference", C.c_int32), ("ba_num_steps", C.c_uint32),
+                ("ba_num_steps_per_run", C.c_uint32), ("ba_min_steps", C.c_uint32), ("ba_huber_width", C.c_float),
+                ("ba_huber_width_scale", C.c_float), ("ba_max_outlier_error", C.c_float),
+                ("ba_max_outlier_error_scale_factor", C.c_float), ("ba_min_mean_square_error", C.c_float),
+                ("ba_distance_tether_weight", C.c_float), ("ba_low_connectivity_iterations_scale", C.c_float)]
+
+    @classmethod
+    def make(cls, **kw):
+        return cls(struct_size=C.sizeof(cls), **kw)
+
+
+class StereoMapInitResultC(C.Structure):
+    """mage_stereo_map_init_result (include/mage_hot.h)."""
+    _fields_ = [("code", C.c_int32), ("crop", C.c_int32 * 4), ("n_masked", C.c_uint32), ("n_matches", C.c_uint32),
+                ("n_verdicts", C.c_uint32), ("frame1_pos3", C.c_float * 3), ("frame1_r9", C.c_float * 9),
+                ("n_points", C.c_uint32), ("n_ba_outliers", C.c_uint32), ("ba_runs", C.c_uint32)]
+
+
 class BAStats(C.Structure):
     _fields_ = [("iterations", C.c_uint64), ("trials", C.c_uint64), ("rejected_trials", C.c_uint64),
                 ("last_chi2", C.c_double), ("lambda_", C.c_double)]
@@ -147,6 +174,10 @@ DM_DTYPE = np.dtype([("query_idx", "<i4"), ("train_idx", "<i4"), ("img_idx", "<i
 # mage_new_point (48 B)
 NP_DTYPE = np.dtype([("position", "<f4", 3), ("mean_view_dir", "<f4", 3), ("d_min", "<f4"), ("d_max", "<f4"),
                      ("ki_index", "<u4"), ("kc_slot", "<u4"), ("kc_index", "<u4"), ("match_index", "<u4")])
+
+# mage_stereo_point (28 B)
+SP_DTYPE = np.dtype([("query_idx", "<i4"), ("train_idx", "<i4"), ("distance", "<f4"), ("position", "<f4", 3),
+                     ("near_parallel", "<u4")])
 
 # mage_new_point_assoc (16 B)
 NA_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("octave", "<i4"), ("keypoint", "<i4")])
@@ -279,3 +310,12 @@ def _declare(L: C.CDLL) -> None:
         vp)
     sig("mage_new_points_associate_batch_device", st, vp, vp, u32, u32, vp, u32, vp, vp, i64, vp, vp, vp, vp, vp, vp,
         vp, vp, i64, vp, vp, vp, vp, vp, vp)
+    sig("mage_stereo_init_triangulate_batch_device", st, vp, u32, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp,
+        vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp)
+    sig("mage_stereo_init_triangulate_host", st, vp, vp, vp, vp, vp, vp, u32, vp, u32, vp, u32, vp, vp, vp, vp, u32,
+        vp, vp, vp, vp, vp, vp, vp)
+    sig("mage_stereo_init_triangulate", st, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp,
+        u32, vp, vp, vp, vp, vp, vp, vp, C.c_int)
+    sig("mage_overlap_crop_source_in_target", st, vp, vp, vp, f32, vp)
+    sig("mage_stereo_map_init", st, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp, C.c_int)
+    sig("mage_debug_stereo_init_host", st, vp, vp, vp, vp, vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp)

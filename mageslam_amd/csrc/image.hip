@@ -463,14 +463,18 @@ void camera_matrix(const mage_camera_config& c, float K[9])
 // ScaleImageForCameraConfiguration's geometry (ImagePreprocessor.cpp:32-57 with
 // CalculateOverlapCropSourceInTarget, MageUtil.cpp:13-58, UnProject / ProjectUndistorted,
 // Utils/cv.h:270-278 and Reprojection.cpp:26-42, IsEntirelyOffscreen, Utils/cv.h:405-418).
-mage_status scale_geometry(const mage_camera_config& src, const mage_camera_config& tgt, float depth, int crop[4],
-                           float* scale, mage_camera_config* prepared, int* ok)
+// The cv::Matx44f arithmetic above for the stereo initialiser's host scalars (stereoinit.cpp).
+void matx44f_mul(const float* a, const float* b, float* out) { matx_mul(a, b, out, 4, 4, 4); }
+void matx44f_inverse(const float* a, float* out) { matx44_inv_lu(a, out); }
+void matx44f_rigid_inverse(const float* t, float* out) { rigid_invert(t, out); }
+
+// CalculateOverlapCropSourceInTarget (MageUtil.cpp:13-58) from targetToSource itself: the part of
+// the geometry StereoMapInit::Initialize calls on frame0ToFrame1 (StereoMapInit.cpp:100).
+mage_status overlap_crop(const float t2s[16], const mage_camera_config& src, const mage_camera_config& tgt, float depth,
+                         int crop[4])
 {
     MAGE_REQUIRE(src.width > 0 && src.height > 0 && tgt.width > 0 && tgt.height > 0, MAGE_EINVAL,
                  "camera configurations need a nonzero size");
-    float tinv[16], t2s[16];
-    matx44_inv_lu(tgt.extrinsics, tinv);
-    matx_mul(src.extrinsics, tinv, t2s, 4, 4, 4);  // targetToSource
     float Ks[9], Ksi[9], Kt[9], view_inv[16];
     camera_matrix(src, Ks);
     matx33_inv(Ks, Ksi);
@@ -507,6 +511,19 @@ mage_status scale_geometry(const mage_camera_config& src, const mage_camera_conf
     crop[1] = (int)mny;
     crop[2] = (int)(size_t)width;
     crop[3] = (int)(size_t)height;
+    return MAGE_OK;
+}
+
+mage_status scale_geometry(const mage_camera_config& src, const mage_camera_config& tgt, float depth, int crop[4],
+                           float* scale, mage_camera_config* prepared, int* ok)
+{
+    MAGE_REQUIRE(src.width > 0 && src.height > 0 && tgt.width > 0 && tgt.height > 0, MAGE_EINVAL,
+                 "camera configurations need a nonzero size");
+    float tinv[16], t2s[16];
+    matx44_inv_lu(tgt.extrinsics, tinv);
+    matx_mul(src.extrinsics, tinv, t2s, 4, 4, 4);  // targetToSource
+    const mage_status r = overlap_crop(t2s, src, tgt, depth, crop);
+    if (r != MAGE_OK) return r;
     const int maxh = crop[2] + crop[0] - 1, maxv = crop[3] + crop[1] - 1;
     const bool offx = maxh < 0 || crop[0] > (int)(tgt.width - 1);
     const bool offy = maxv < 0 || crop[1] > (int)(tgt.height - 1);
@@ -546,6 +563,17 @@ mage_status mage_scale_for_camera_configuration(const mage_camera_config* source
     mage_status r = mage::scale_geometry(*source, *target, max_depth_meters, crop, scale, prepared, &k);
     for (int i = 0; i < 4; i++) crop_xywh[i] = crop[i];
     *ok = k;
+    return r;
+}
+
+mage_status mage_overlap_crop_source_in_target(const float target_to_source[16], const mage_camera_config* target,
+                                               const mage_camera_config* source, float depth_meters,
+                                               int32_t crop_xywh[4])
+{
+    MAGE_REQUIRE(target_to_source && target && source && crop_xywh, MAGE_EINVAL, "null argument");
+    int crop[4] = {0, 0, 0, 0};
+    const mage_status r = mage::overlap_crop(target_to_source, *source, *target, depth_meters, crop);
+    for (int i = 0; i < 4; i++) crop_xywh[i] = crop[i];
     return r;
 }
 
