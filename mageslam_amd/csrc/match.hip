@@ -500,8 +500,9 @@ constexpr int NRES = 2560;  // B descriptors kept resident in LDS up to this cou
 // ------------------------------------------------------------------------------------------
 // fp4 matcher (nb <= 2048, maxDist < 128, minDiff >= 1: every practical call, C2 included).
 //
-// 8 waves (2 per SIMD, 249 VGPRs), four 32-row A tiles each per pass; one column flush (partner
-// half, LDS atomics) per two tiles (64 rows: the 6-bit row code).  2000 rows are 63 row tiles:
+// 8 waves (2 per SIMD, 256 VGPRs), four 32-row A tiles each per pass; one column flush (two LDS
+// atomics per lane, each half-wave on its own rows: MAGE_FP4_FLUSH_HALVES) per two tiles (64 rows:
+// the 6-bit row code).  2000 rows are 63 row tiles:
 // 8 waves x 4 run them in 2 passes with one wave slot idle (98 % of the slots busy), 12 x 2 in 3
 // passes with 9 idle (88 %).  Measured on C2 (tools/abl.py, 256 pairs, one box): 12 x 2 0.234-0.240
 // ms, 8 x 4 0.227-0.229 (8 x 4 with 4 / 1 fill columns per thread 0.229 / 0.230, 16 x 2 0.288
@@ -538,7 +539,8 @@ constexpr int FSC = FCOLS * FSC1;    // B columns per LDS stage
 constexpr int FNT = FSC / 32;        // column tiles per stage
 constexpr int FNB = 2048;            // max B descriptors
 constexpr int FNA = 4096;            // max A descriptors
-constexpr int FBUF = FCOLS == 1 ? 3 : 2;  // stage buffers (LDS: 160 KB per CU)
+constexpr int FBUF = FCOLS == 1 ? 3 : 2;  // stage buffers (LDS: 160 KB = 163,840 B per CU; the kernel
+                                          // takes 122,912 B, 123,936 B with MAGE_FP4_LUT's 1 KB table)
 constexpr int FPF = FBUF - 1;        // stages filled ahead
 constexpr uint32_t K16_BASE = 0x2400u;  // low-16 mantissa offset of the accumulator start
 constexpr int K16_D = 272;           // key >> 6 = K16_D - d
@@ -551,6 +553,27 @@ constexpr uint32_t NONE16 = 0x80008000u;
 // fold is not what bounds the kernel once the gate's branch breaks the overlap of the MFMAs with
 // the fold — while rBRIEF-31's sparser candidates would gain 0.23 -> 0.16 ms.
 #define MAGE_FP4_GATE 0
+#endif
+#ifndef MAGE_FP4_FLUSH_HALVES
+// 1: both half-waves flush their own column partial (lanes l and l + 32 hold the same column, rows
+// r and r + 4; the row code in each key already carries the + 4).  The two-atomic protocol is exact
+// for any number of contributors to a column, so the v_permlane32_swap merge of the halves (about
+// 22 VALU per flush; the kernel's static VALU count 2569 -> 2480) goes; the price is two lanes per
+// LDS address in each atomic.  0: merge the halves first, lanes 0-31 flush.  Measured (tools/abl.py,
+// 256 C2 pairs, variants alternated, five runs each): 0.2239-0.2301 -> 0.2129-0.2203 ms, and in a
+// second job 0.2243-0.2273 -> 0.2106-0.2188 (profiles/r8_match_valu.md).
+#define MAGE_FP4_FLUSH_HALVES 1
+#endif
+#ifndef MAGE_FP4_LUT
+// fp4 operands from a 256-entry LDS table (entry b = the output dword of descriptor byte b,
+// filled once per workgroup with expand32_fp4): 4 byte extractions + 4 ds_read_b32 per descriptor
+// dword instead of about 36 VALU.  Bit 0: the A operands of a pass, bit 1: the B stage fill.  Exact
+// either way, but off: it removes 15-20 % of the kernel's static VALU (2480 -> 2092 / 2392 / 1991
+// for 1 / 2 / 3) and no time.  Measured as above, beside the half-wave flush's 0.2106-0.2188 ms:
+// 1 0.2190-0.2240, 2 0.2139-0.2173, 3 0.2204-0.2234; without the half-wave flush 3 gives
+// 0.2220-0.2273 against the parent's 0.2239-0.2301.  Presumably the lookups (random banks, and a
+// dependent LDS round trip ahead of a barrier) cost what the VALU they replace did.
+#define MAGE_FP4_LUT 0
 #endif
 
 typedef short s16x2 __attribute__((ext_vector_type(2)));
@@ -607,6 +630,9 @@ __global__ __launch_bounds__(FT) void match_fp4_kernel(const uint8_t* __restrict
     __shared__ int colM1[FNB], colM2[FNB];             // column (best, second) global keys
     __shared__ uint16_t rowd[FNA];                     // accepted row: best distance, else 0xFFFF
     __shared__ uint32_t wsum[FW];
+#if MAGE_FP4_LUT
+    __shared__ uint32_t lut[256];                      // fp4 output dword of each descriptor byte
+#endif
     uint16_t* matchOf = reinterpret_cast<uint16_t*>(&stage[0][0][0][0]);  // after the passes
     static_assert(sizeof(stage) >= FNA * sizeof(uint16_t), "matchOf aliases the stages");
 
@@ -630,8 +656,20 @@ __global__ __launch_bounds__(FT) void match_fp4_kernel(const uint8_t* __restrict
     if (na > 0 && nb > 0) {
         for (int k = tid; k < 2 * nb; k += FT) reinterpret_cast<uint4*>(bres)[k] = reinterpret_cast<const uint4*>(Bw)[k];
     }
-    // B resident before the first pass's stage fetches read it (other threads' rows; without this
-    // barrier a fetch could read a row not yet written: test_match_random[513-64] caught it)
+#if MAGE_FP4_LUT
+    if (tid < 256) lut[tid] = (uint32_t)expand32_fp4((uint32_t)tid)[0];
+#endif
+    // the fp4 operands of descriptor dword w; use: 1 = A operands, 2 = stage fill (MAGE_FP4_LUT's bits)
+    auto expand = [&](uint32_t w, int use) -> v4i {
+#if MAGE_FP4_LUT
+        if (MAGE_FP4_LUT & use)
+            return v4i{(int)lut[w & 0xFFu], (int)lut[(w >> 8) & 0xFFu], (int)lut[(w >> 16) & 0xFFu], (int)lut[w >> 24]};
+#endif
+        return expand32_fp4(w);
+    };
+    // B resident (and MAGE_FP4_LUT's table filled) before the first pass's stage fetches read it
+    // (other threads' rows; without this barrier a fetch could read a row not yet written:
+    // test_match_random[513-64] caught it)
     __syncthreads();
     // per-lane accumulator start: register g holds tile row acc_row(g) + 4 h, code 63 - row
     v16f cc;
@@ -654,7 +692,7 @@ __global__ __launch_bounds__(FT) void match_fp4_kernel(const uint8_t* __restrict
 #pragma unroll
         for (int k = 0; k < FCOLS; k++) {
             const int fc = fc0 + k * FSC1;
-            stage[buf][fc >> 5][fs >> 1][32 * (fs & 1) + (fc & 31)] = st * FSC + fc < nb ? expand32_fp4(f.dw[k]) : zero;
+            stage[buf][fc >> 5][fs >> 1][32 * (fs & 1) + (fc & 31)] = st * FSC + fc < nb ? expand(f.dw[k], 2) : zero;
         }
     };
 
@@ -671,7 +709,7 @@ __global__ __launch_bounds__(FT) void match_fp4_kernel(const uint8_t* __restrict
             const uint32_t* ar = Aw + 8 * min(i, na - 1);
             const v4i zero = {0, 0, 0, 0};
 #pragma unroll
-            for (int s = 0; s < 4; s++) a[rt][s] = i < na ? expand32_fp4(ar[2 * s + (lane >> 5)]) : zero;
+            for (int s = 0; s < 4; s++) a[rt][s] = i < na ? expand(ar[2 * s + (lane >> 5)], 1) : zero;
         }
         uint32_t r1[FRT][8], r2[FRT][8];
 #pragma unroll
@@ -762,6 +800,7 @@ __global__ __launch_bounds__(FT) void match_fp4_kernel(const uint8_t* __restrict
                         if (gating && g_tiles >= 64 && 4 * g_hits > g_tiles) gating = false;  // dense: fold all
                         if (!any) continue;  // no key of the column tile within maxDist: no flush
                         const int kg = kadd - 64 * (grp / 2);
+#if !MAGE_FP4_FLUSH_HALVES
                         // the partner half-wave holds the same column (rows + 4)
                         {
                             const uint32_t o1 = (uint32_t)xor32((int)c1, lane), o2 = (uint32_t)xor32((int)c2, lane);
@@ -769,6 +808,7 @@ __global__ __launch_bounds__(FT) void match_fp4_kernel(const uint8_t* __restrict
                             c1 = pkmax(c1, o1);
                             c2 = pkmax3(lo, c2, o2);
                         }
+#endif
                         const int a1 = lo16s(c1), b1 = hi16s(c1);
                         const int m1 = max(a1, b1), m2 = max(min(a1, b1), max(lo16s(c2), hi16s(c2)));
                         const int g1 = ((m1 >> 6) << 16) | ((m1 & 63) + kg);
@@ -777,7 +817,7 @@ __global__ __launch_bounds__(FT) void match_fp4_kernel(const uint8_t* __restrict
                         pc.j = colbase + (lane & 31);
                         pc.c1 = g1;
                         pc.c2 = g2;
-                        pc.live = lane < 32 && pc.j < nb;
+                        pc.live = (MAGE_FP4_FLUSH_HALVES || lane < 32) && pc.j < nb;
                         pc.old = pc.live ? atomicMax(&colM1[pc.j], g1) : NONE;
                     }
                 }
