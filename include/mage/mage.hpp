@@ -627,6 +627,177 @@ private:
     mage_stereo_map_init_result m_last{};
 };
 
+// MonoMapInitializationSettings (MageSettings.h:95-128) with its two OrbMatcherSettings bags.
+struct MonoMapInitializationSettings {
+    float FundamentalTransferErrorThreshold{1.1f};
+    unsigned MinFeatureMatches{65}, MinScoringInliers{50};
+    float MinInlierPercentage{0.5f};
+    unsigned MinInitialMapPoints{40}, MinMapPoints{60};
+    float MinThirdFrameMatchPercentage{0.5f}, FeatureCovisibilityThreshold{0.35f};
+    float MaxParallax3dDistance{500.0f}, MaxParallax3dMedianDistance{20.0f};
+    float MinCandidatePoseDisimilarity{0.3f}, MaxPoseContributionZ{0.66f};
+    unsigned BundleAdjustmentG2OSteps{5};
+    float BundleAdjustmentHuberWidth{1.5f};
+    unsigned RansacIterationsForModels{90};
+    float MaxEpipolarError{3.5f}, MaxOutlierError{2.5f}, AmountBACanChangePose{1.65f};
+    float MapInitializationNewPointsCreationMinDistance{0.25f};
+    unsigned MapInitFrameIntervalMilliseconds{0}, MinInitializationIntervalMilliseconds{150};
+    unsigned MaxInitializationIntervalMilliseconds{540};
+    float MinPixelSpread{40.0f};
+    float FinalBA_HuberWidth{0.9f}, FinalBA_MaxOutlierError{4.0f}, FinalBA_MaxOutlierErrorScaleFactor{0.75f};
+    float FinalBA_MinMeanSquareError{0.0f};
+    unsigned FinalBA_NumStepsPerRun{5}, FinalBA_NumSteps{15};
+    float ExtraFrame_MaxOutlierError{8.0f};
+    unsigned ExtraFrame_BundleAdjustmentSteps{5};
+    float ExtraFrame_HuberWidth{4.0f}, ExtraFrame_SearchRadius{40.0f};
+    struct {
+        int MaxHammingDistance{30}, MinHammingDifference{1};
+    } FivePointMatchingSettings, ExtraFrameMatchingSettings;
+
+    mage_mono_init_settings ToC() const
+    {
+        mage_mono_init_settings s{};
+        s.struct_size = (uint32_t)sizeof(s);
+        s.fundamental_transfer_error_threshold = FundamentalTransferErrorThreshold;
+        s.min_feature_matches = MinFeatureMatches;
+        s.min_scoring_inliers = MinScoringInliers;
+        s.min_inlier_percentage = MinInlierPercentage;
+        s.min_initial_map_points = MinInitialMapPoints;
+        s.min_map_points = MinMapPoints;
+        s.min_third_frame_match_percentage = MinThirdFrameMatchPercentage;
+        s.feature_covisibility_threshold = FeatureCovisibilityThreshold;
+        s.max_parallax_3d_distance = MaxParallax3dDistance;
+        s.max_parallax_3d_median_distance = MaxParallax3dMedianDistance;
+        s.min_candidate_pose_disimilarity = MinCandidatePoseDisimilarity;
+        s.max_pose_contribution_z = MaxPoseContributionZ;
+        s.bundle_adjustment_g2o_steps = BundleAdjustmentG2OSteps;
+        s.bundle_adjustment_huber_width = BundleAdjustmentHuberWidth;
+        s.ransac_iterations_for_models = RansacIterationsForModels;
+        s.max_epipolar_error = MaxEpipolarError;
+        s.max_outlier_error = MaxOutlierError;
+        s.amount_ba_can_change_pose = AmountBACanChangePose;
+        s.map_initialization_new_points_creation_min_distance = MapInitializationNewPointsCreationMinDistance;
+        s.map_init_frame_interval_milliseconds = MapInitFrameIntervalMilliseconds;
+        s.min_initialization_interval_milliseconds = MinInitializationIntervalMilliseconds;
+        s.max_initialization_interval_milliseconds = MaxInitializationIntervalMilliseconds;
+        s.min_pixel_spread = MinPixelSpread;
+        s.final_ba_huber_width = FinalBA_HuberWidth;
+        s.final_ba_max_outlier_error = FinalBA_MaxOutlierError;
+        s.final_ba_max_outlier_error_scale_factor = FinalBA_MaxOutlierErrorScaleFactor;
+        s.final_ba_min_mean_square_error = FinalBA_MinMeanSquareError;
+        s.final_ba_num_steps_per_run = FinalBA_NumStepsPerRun;
+        s.final_ba_num_steps = FinalBA_NumSteps;
+        s.extra_frame_max_outlier_error = ExtraFrame_MaxOutlierError;
+        s.extra_frame_bundle_adjustment_steps = ExtraFrame_BundleAdjustmentSteps;
+        s.extra_frame_huber_width = ExtraFrame_HuberWidth;
+        s.extra_frame_search_radius = ExtraFrame_SearchRadius;
+        s.five_point_max_hamming_distance = FivePointMatchingSettings.MaxHammingDistance;
+        s.five_point_min_hamming_difference = FivePointMatchingSettings.MinHammingDifference;
+        s.extra_frame_max_hamming_distance = ExtraFrameMatchingSettings.MaxHammingDistance;
+        s.extra_frame_min_hamming_difference = ExtraFrameMatchingSettings.MinHammingDifference;
+        return s;
+    }
+};
+
+// What MapInitialization::InitializeWithFrames reads of an AnalyzedImage: the undistorted
+// calibration {cx, cy, fx, fy}, the undistorted keypoints and (for the matcher) their descriptors.
+struct MonoFrame {
+    std::array<float, 4> Intrinsics;
+    const std::vector<KeyPoint>* KeyPoints;
+    const uint8_t* Descriptors{nullptr};  // n x 32 bytes, or null when the matches are given
+};
+
+// The reference's InitializationData after InitializeWithFrames (MapInitialization.cpp:1030-1091):
+// the reference frame's builder at the identity, the current frame's at Frame1Position /
+// Frame1Rotation (view-space t, column-major R), and the map points in match order; MapPoints[i] is
+// associated with keypoint query_idx of the reference frame and train_idx of the current frame.
+// The Bundle* arrays are BundleAdjustInitializationData's inputs for these two frames.
+struct MonoInitializationData {
+    std::array<float, 3> Frame1Position;
+    std::array<float, 9> Frame1Rotation;
+    std::vector<StereoPoint> MapPoints;
+    std::vector<float> BundlePoints, BundleObservations, BundleInformation;
+    std::vector<uint32_t> BundleCameras, BundleMapPoints;
+};
+
+// The two-view stage of MapInitialization (Tracking/MapInitialization.h) over mage_mono_init_two_view.
+class MonoMapInit {
+public:
+    // device < 0 runs the CPU backend, which needs the matches.
+    explicit MonoMapInit(const MonoMapInitializationSettings& settings, int device = 0)
+        : m_settings(settings.ToC()), m_device(device)
+    {
+    }
+
+    // InitializeWithFrames (MapInitialization.cpp:988-1094) for the caller's bestMatches (queryIdx in
+    // the reference frame, trainIdx in the current frame); with `matches` null the octave-0 masks
+    // and Match of :562-588 run first (a device and both descriptor sets are needed).  std::nullopt
+    // where the reference returns false; LastResult().verdict then says why (MAGE_MI_*) and
+    // LastMatches() holds the matches the stage ran on.  Throws where the reference asserts or would
+    // read out of bounds: a match that names no keypoint (std::out_of_range), more than 4096
+    // keypoints or matches (Error, MAGE_EUNSUPPORTED).
+    std::optional<MonoInitializationData> InitializeWithFrames(const std::vector<DMatch>* matches,
+                                                               const MonoFrame& referenceFrame,
+                                                               const MonoFrame& currentFrame)
+    {
+        if (!matches && (m_device < 0 || !referenceFrame.Descriptors || !currentFrame.Descriptors))
+            throw std::invalid_argument("without matches both descriptor sets and a device are needed");
+        const uint32_t n0 = (uint32_t)referenceFrame.KeyPoints->size(), n1 = (uint32_t)currentFrame.KeyPoints->size();
+        float intr[8];
+        std::copy(referenceFrame.Intrinsics.begin(), referenceFrame.Intrinsics.end(), intr);
+        std::copy(currentFrame.Intrinsics.begin(), currentFrame.Intrinsics.end(), intr + 4);
+        m_matches = matches ? *matches : std::vector<DMatch>();
+        uint32_t nm = (uint32_t)m_matches.size();
+        const uint32_t cap = std::max<uint32_t>(matches ? nm : std::min<uint32_t>(n0, 4096u), 1);
+        m_matches.resize(cap);
+        MonoInitializationData d;
+        d.MapPoints.resize(cap);
+        d.BundlePoints.resize(3 * (size_t)cap);
+        d.BundleObservations.resize(4 * (size_t)cap);
+        d.BundleInformation.resize(2 * (size_t)cap);
+        d.BundleCameras.resize(2 * (size_t)cap);
+        d.BundleMapPoints.resize(2 * (size_t)cap);
+        m_last = mage_mono_init_result{};
+        if (m_device < 0)
+            check(mage_mono_init_two_view_host(&m_settings, intr, referenceFrame.KeyPoints->data(), n0,
+                                               currentFrame.KeyPoints->data(), n1, m_matches.data(), nm, &m_last,
+                                               d.MapPoints.data(), cap, d.BundlePoints.data(),
+                                               d.BundleObservations.data(), d.BundleCameras.data(),
+                                               d.BundleMapPoints.data(), d.BundleInformation.data(), nullptr));
+        else
+            check(mage_mono_init_two_view(&m_settings, intr, referenceFrame.KeyPoints->data(),
+                                          matches ? nullptr : referenceFrame.Descriptors, n0,
+                                          currentFrame.KeyPoints->data(), matches ? nullptr : currentFrame.Descriptors,
+                                          n1, m_matches.data(), cap, &nm, &m_last, d.MapPoints.data(), cap,
+                                          d.BundlePoints.data(), d.BundleObservations.data(), d.BundleCameras.data(),
+                                          d.BundleMapPoints.data(), d.BundleInformation.data(), nullptr, m_device));
+        m_matches.resize(nm);
+        if (m_last.status & MAGE_MI_STATUS_OVER_LIMIT)
+            throw Error(MAGE_EUNSUPPORTED, "more than 4096 keypoints in a frame or more than 4096 matches");
+        if (m_last.status & MAGE_MI_STATUS_BAD_INDEX) throw std::out_of_range("a match names no keypoint");
+        if (m_last.verdict != MAGE_MI_OK) return std::nullopt;
+        const size_t n = m_last.n_points;
+        std::copy(m_last.pos3 + 3, m_last.pos3 + 6, d.Frame1Position.begin());
+        std::copy(m_last.r9 + 9, m_last.r9 + 18, d.Frame1Rotation.begin());
+        d.MapPoints.resize(n);
+        d.BundlePoints.resize(3 * n);
+        d.BundleObservations.resize(4 * n);
+        d.BundleInformation.resize(2 * n);
+        d.BundleCameras.resize(2 * n);
+        d.BundleMapPoints.resize(2 * n);
+        return d;
+    }
+
+    const mage_mono_init_result& LastResult() const { return m_last; }
+    const std::vector<DMatch>& LastMatches() const { return m_matches; }
+
+private:
+    mage_mono_init_settings m_settings;
+    int m_device;
+    mage_mono_init_result m_last{};
+    std::vector<DMatch> m_matches;
+};
+
 struct BundlerParameters {
     bool ArePointsFixed{false};
 };

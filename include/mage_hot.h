@@ -796,6 +796,161 @@ mage_status mage_debug_stereo_init_host(const mage_stereo_init_settings* setting
                                         const float* ba_r9, int32_t* valid);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Monocular map initialisation — the two-view geometry of                                     */
+/* MapInitialization::InitializeWithFrames (Core/.../Tracking/MapInitialization.cpp:988-1094)  */
+/* ------------------------------------------------------------------------------------------ */
+
+/* MonoMapInitializationSettings (MageSettings.h:95-128) in the reference's order: its scalars, then
+ * its two OrbMatcherSettings bags (FivePointMatchingSettings, ExtraFrameMatchingSettings).
+ * struct_size must be sizeof(mage_mono_init_settings); anything else is MAGE_EINVAL.  The two-view
+ * stage reads the fields marked (*); the others belong to the rest of
+ * TryIntializeMapWithProvidedFrames (new points, the bundle adjustments, the third frame,
+ * validation) and are carried for it. */
+typedef struct mage_mono_init_settings {
+    uint32_t struct_size;
+    float fundamental_transfer_error_threshold;  /* (*) FundamentalTransferErrorThreshold 1.1 */
+    uint32_t min_feature_matches;                /* (*) MinFeatureMatches 65, at least 5 */
+    uint32_t min_scoring_inliers;                /* (*) MinScoringInliers 50 */
+    float min_inlier_percentage;                 /* (*) MinInlierPercentage 0.5 */
+    uint32_t min_initial_map_points;             /* MinInitialMapPoints 40 */
+    uint32_t min_map_points;                     /* MinMapPoints 60 */
+    float min_third_frame_match_percentage;      /* MinThirdFrameMatchPercentage 0.5 */
+    float feature_covisibility_threshold;        /* FeatureCovisibilityThreshold 0.35 */
+    float max_parallax_3d_distance;              /* (*) MaxParallax3dDistance 500 */
+    float max_parallax_3d_median_distance;       /* (*) MaxParallax3dMedianDistance 20 */
+    float min_candidate_pose_disimilarity;       /* (*) MinCandidatePoseDisimilarity 0.3 */
+    float max_pose_contribution_z;               /* (*) MaxPoseContributionZ 0.66 */
+    uint32_t bundle_adjustment_g2o_steps;        /* BundleAdjustmentG2OSteps 5 */
+    float bundle_adjustment_huber_width;         /* BundleAdjustmentHuberWidth 1.5 */
+    uint32_t ransac_iterations_for_models;       /* (*) RansacIterationsForModels 90, in 1..256 */
+    float max_epipolar_error;                    /* (*) MaxEpipolarError 3.5 */
+    float max_outlier_error;                     /* MaxOutlierError 2.5 */
+    float amount_ba_can_change_pose;             /* AmountBACanChangePose 1.65 */
+    float map_initialization_new_points_creation_min_distance; /* ...NewPointsCreationMinDistance 0.25 */
+    uint32_t map_init_frame_interval_milliseconds;       /* MapInitFrameIntervalMilliseconds 0 */
+    uint32_t min_initialization_interval_milliseconds;   /* MinInitializationIntervalMilliseconds 150 */
+    uint32_t max_initialization_interval_milliseconds;   /* MaxInitializationIntervalMilliseconds 540 */
+    float min_pixel_spread;                      /* (*) MinPixelSpread 40 */
+    float final_ba_huber_width;                  /* FinalBA_HuberWidth 0.9 */
+    float final_ba_max_outlier_error;            /* FinalBA_MaxOutlierError 4 */
+    float final_ba_max_outlier_error_scale_factor; /* FinalBA_MaxOutlierErrorScaleFactor 0.75 */
+    float final_ba_min_mean_square_error;        /* FinalBA_MinMeanSquareError 0 */
+    uint32_t final_ba_num_steps_per_run;         /* FinalBA_NumStepsPerRun 5 */
+    uint32_t final_ba_num_steps;                 /* FinalBA_NumSteps 15 */
+    float extra_frame_max_outlier_error;         /* ExtraFrame_MaxOutlierError 8 */
+    uint32_t extra_frame_bundle_adjustment_steps; /* ExtraFrame_BundleAdjustmentSteps 5 */
+    float extra_frame_huber_width;               /* ExtraFrame_HuberWidth 4 */
+    float extra_frame_search_radius;             /* ExtraFrame_SearchRadius 40 */
+    int32_t five_point_max_hamming_distance;     /* (*) FivePointMatchingSettings.MaxHammingDistance 30 */
+    int32_t five_point_min_hamming_difference;   /* (*) FivePointMatchingSettings.MinHammingDifference 1 */
+    int32_t extra_frame_max_hamming_distance;    /* ExtraFrameMatchingSettings.MaxHammingDistance 30 */
+    int32_t extra_frame_min_hamming_difference;  /* ExtraFrameMatchingSettings.MinHammingDifference 1 */
+} mage_mono_init_settings;
+
+/* A pair's verdict: InitializeWithFrames' reasons to give up, in its order. */
+#define MAGE_MI_OK 0
+#define MAGE_MI_FEW_MATCHES 1   /* fewer than MinFeatureMatches matches (:592, :1002) */
+#define MAGE_MI_NO_HYPOTHESIS 2 /* FindPossiblePoses returned nothing (:1014-1019) */
+#define MAGE_MI_NO_VALID_POSE 3 /* FindCorrectPose: no pose with a valid score (:453) */
+#define MAGE_MI_TOO_SIMILAR 4   /* the best two poses' scores are too similar (:460-465) */
+#define MAGE_MI_Z_BIASED 5      /* the best pose moves too much along Z (:468-472) */
+
+/* Bits of a pair's status word. */
+#define MAGE_MI_STATUS_OVER_LIMIT 1u /* over 4096 keypoints in a frame or over its pitch, over 4096 matches or over match_cap */
+#define MAGE_MI_STATUS_OVER_CAP 2u   /* more accepted matches than `cap` (the count reports cap) */
+#define MAGE_MI_STATUS_BAD_INDEX 4u  /* a given match names no keypoint */
+
+/* Bits of mage_mono_init_result.cand_flags. */
+#define MAGE_MI_POSE_TWISTED 1u   /* skipped: its right vector opposes the reference's (:362) */
+#define MAGE_MI_POSE_ENOUGH 2u    /* passed the MinScoringInliers / MinInlierPercentage gate (:419) */
+#define MAGE_MI_POSE_MEDIAN_OK 4u /* its median depth is within MaxParallax3dMedianDistance (:433) */
+
+/* What the two-view stage decides for one pair; written whole for every pair, zero where a stage
+ * was not reached.  Poses are as mage_ba_set_cameras takes them: view-space t and column-major R. */
+typedef struct mage_mono_init_result {
+    uint32_t verdict;    /* MAGE_MI_* */
+    uint32_t status;     /* MAGE_MI_STATUS_* bits; with OVER_LIMIT or BAD_INDEX nothing else of the pair is written */
+    uint32_t n_matches;  /* the matches the stage ran on */
+    uint32_t n_points;   /* accepted records (at most cap); 0 unless the verdict is MAGE_MI_OK */
+    int32_t win_iteration, win_root; /* FindPossiblePoses' winner: RANSAC iteration and root, or -1 */
+    int32_t win_indices[5];          /* its five matches, ascending */
+    float win_score;                 /* its ScoreFundamentalMatrix */
+    int32_t selected_pose;           /* FindCorrectPose's selectedPoseIndex, or -1 */
+    float next_best_score;           /* its nextBestPoseScore */
+    float pos3[6], r9[18];           /* frame 0 (the identity) and frame 1 (the selected pose when OK, else the identity) */
+    float cand_pos3[12], cand_r9[36]; /* FindEssentialPotientialPoses' four poses of the winner, in its order */
+    float cand_score[4];             /* FindCorrectPose's score per pose */
+    float cand_median[4];            /* its median depth (0 unless MAGE_MI_POSE_ENOUGH) */
+    uint32_t cand_count[4];          /* its candidatePosePoints.size() */
+    uint32_t cand_flags[4];          /* MAGE_MI_POSE_* */
+} mage_mono_init_result;
+
+/* Bytes of one pair's trace for `iterations` RANSAC iterations, arrays in this order:
+ *   int32 indices[iterations][5]    the sample's matches, ascending, or -1 five times (no sample);
+ *   int32 candidates[iterations]    essential matrices the five-point solver returned (0..10);
+ *   float E[iterations][10][9]      they, row-major, in root order; zero past the count;
+ *   float score[iterations][10]     ScoreFundamentalMatrix (0 when gated out or past the count);
+ *   uint32 inliers[iterations][10]  its inlier count;
+ *   uint32 cheirality[iterations][10]  1 when HasConsistentCheirality on the sample's points.
+ * 504 bytes per iteration. */
+uint64_t mage_mono_init_trace_bytes(uint32_t iterations);
+
+/* Bytes of mage_mono_init_two_view_batch_device's scratch: the work buffer (pairs traces, when no
+ * trace is given) and, with the matcher, the packed octave-0 descriptors of both frames with their
+ * keypoint indices and counts. */
+uint64_t mage_mono_init_scratch_bytes(uint32_t iterations, uint32_t pairs, int64_t pitch0, int64_t pitch1,
+                                      int32_t with_trace, int32_t with_matcher);
+
+/* The two-view stage for `pairs` frame pairs, launches on `stream` with no host step between them:
+ *   m. (with descriptors) the octave-0 masks of :562-583 for both frames, their descriptors packed
+ *      in keypoint order, Match (:585) by mage_hamming_match_batch_device with
+ *      FivePointMatchingSettings, and the indices mapped back to keypoints: d_matches /
+ *      d_n_matches then hold Match's result.  With d_desc0 == NULL they are inputs — the caller's
+ *      bestMatches after its covisibility counters (:611-623), which stay caller-side.
+ *   a. CollectMatchPoints (:889-909) and FindPossiblePoses' sampler (:196-249).
+ *   b. the five-point solver per hypothesis (Tracking/ComputeEssential.cpp:357-514).
+ *   c. ScoreFundamentalMatrix (:279-322) and HasConsistentCheirality (:129-179) per candidate.
+ *   d. the winner (the earliest maximum score among the consistent candidates), its four poses
+ *      (:85-114), FindCorrectPose (:324-480), and for MAGE_MI_OK the accepted matches of the selected
+ *      pose compacted in match order at d_out + pair * cap with the bundle adjustment's inputs laid
+ *      out as mage_stereo_init_triangulate_batch_device lays them out (frame-major, info =
+ *      MapPointRefinementConfidence(1)).
+ * Per pair: d_intr4 8 floats = {cx, cy, fx, fy} of frame 0 then frame 1; frame f's keypoints and
+ * 32-byte descriptors pitch0 / pitch1 entries per pair, counts d_n0 / d_n1; d_matches match_cap
+ * records per pair.  d_trace: NULL, or pairs x mage_mono_init_trace_bytes(iterations) bytes.
+ * d_scratch: mage_mono_init_scratch_bytes(...) bytes, 16-byte aligned like the descriptors; may be
+ * NULL when that is 0.  Nothing is written past a pair's counts: records and points past
+ * n_points, observations past 2 n_points; the trace of a pair that stops before (a) (over a limit,
+ * a bad index, too few matches) is left untouched.  The other pairs are unaffected. */
+mage_status mage_mono_init_two_view_batch_device(
+    const mage_mono_init_settings* settings, uint32_t pairs, const float* d_intr4, const mage_keypoint* d_kp0,
+    const uint8_t* d_desc0, int64_t pitch0, const uint32_t* d_n0, const mage_keypoint* d_kp1, const uint8_t* d_desc1,
+    int64_t pitch1, const uint32_t* d_n1, mage_dmatch* d_matches, uint32_t match_cap, uint32_t* d_n_matches,
+    mage_mono_init_result* d_result, mage_stereo_point* d_out, uint32_t cap, float* d_ba_points, float* d_ba_uv,
+    uint32_t* d_ba_cam, uint32_t* d_ba_pt, float* d_ba_info, void* d_trace, void* d_scratch, mage_stream stream);
+
+/* One pair, host buffers, synchronous, runs on `device`: arrays as one pair of the batched form.
+ * With desc0 / desc1 (n x 32 bytes) the matcher runs and `matches` (match_cap records, at least
+ * one) and *n_matches are outputs; with desc0 == NULL the first *n_matches records are the input.
+ * out and ba_* sized for cap points; trace NULL or mage_mono_init_trace_bytes(iterations) bytes. */
+mage_status mage_mono_init_two_view(const mage_mono_init_settings* settings, const float* intr4,
+                                    const mage_keypoint* kp0, const uint8_t* desc0, uint32_t n0,
+                                    const mage_keypoint* kp1, const uint8_t* desc1, uint32_t n1, mage_dmatch* matches,
+                                    uint32_t match_cap, uint32_t* n_matches, mage_mono_init_result* result,
+                                    mage_stereo_point* out, uint32_t cap, float* ba_points, float* ba_uv,
+                                    uint32_t* ba_cam, uint32_t* ba_pt, float* ba_info, void* trace, int device);
+
+/* Stages (a) to (d) for one pair in plain C++ on the calling thread, the matches given: the
+ * reference's sequential loops over the same arithmetic, the CPU backend, bit-identical to the
+ * kernels.  No GPU. */
+mage_status mage_mono_init_two_view_host(const mage_mono_init_settings* settings, const float* intr4,
+                                         const mage_keypoint* kp0, uint32_t n0, const mage_keypoint* kp1, uint32_t n1,
+                                         const mage_dmatch* matches, uint32_t n_matches,
+                                         mage_mono_init_result* result, mage_stereo_point* out, uint32_t cap,
+                                         float* ba_points, float* ba_uv, uint32_t* ba_cam, uint32_t* ba_pt,
+                                         float* ba_info, void* trace);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Local bundle adjustment — replaces BundlerLib (Dependencies/BundlerLib/Include/BundlerLib.h) */
 /* ------------------------------------------------------------------------------------------ */
 

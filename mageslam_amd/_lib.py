@@ -42,6 +42,8 @@ EXPORTS = [
     "mage_new_points_associate", "mage_new_points_associate_host", "mage_new_points_associate_batch_device",
     "mage_stereo_map_init", "mage_debug_stereo_init_host",
     "mage_stereo_init_triangulate", "mage_stereo_init_triangulate_batch_device", "mage_stereo_init_triangulate_host",
+    "mage_mono_init_trace_bytes", "mage_mono_init_scratch_bytes",
+    "mage_mono_init_two_view", "mage_mono_init_two_view_batch_device", "mage_mono_init_two_view_host",
 ]
 
 
@@ -155,6 +157,35 @@ class StereoInitSettingsC(C.Structure):
         return cls(struct_size=C.sizeof(cls), **kw)
 
 
+class MonoInitSettingsC(C.Structure):
+    """mage_mono_init_settings (include/mage_hot.h); struct_size is filled in by make()."""
+    _fields_ = [("struct_size", C.c_uint32), ("fundamental_transfer_error_threshold", C.c_float),
+                ("min_feature_matches", C.c_uint32), ("min_scoring_inliers", C.c_uint32),
+                ("min_inlier_percentage", C.c_float), ("min_initial_map_points", C.c_uint32),
+                ("min_map_points", C.c_uint32), ("min_third_frame_match_percentage", C.c_float),
+                ("feature_covisibility_threshold", C.c_float), ("max_parallax_3d_distance", C.c_float),
+                ("max_parallax_3d_median_distance", C.c_float), ("min_candidate_pose_disimilarity", C.c_float),
+                ("max_pose_contribution_z", C.c_float), ("bundle_adjustment_g2o_steps", C.c_uint32),
+                ("bundle_adjustment_huber_width", C.c_float), ("ransac_iterations_for_models", C.c_uint32),
+                ("max_epipolar_error", C.c_float), ("max_outlier_error", C.c_float),
+                ("amount_ba_can_change_pose", C.c_float),
+                ("map_initialization_new_points_creation_min_distance", C.c_float),
+                ("map_init_frame_interval_milliseconds", C.c_uint32),
+                ("min_initialization_interval_milliseconds", C.c_uint32),
+                ("max_initialization_interval_milliseconds", C.c_uint32), ("min_pixel_spread", C.c_float),
+                ("final_ba_huber_width", C.c_float), ("final_ba_max_outlier_error", C.c_float),
+                ("final_ba_max_outlier_error_scale_factor", C.c_float), ("final_ba_min_mean_square_error", C.c_float),
+                ("final_ba_num_steps_per_run", C.c_uint32), ("final_ba_num_steps", C.c_uint32),
+                ("extra_frame_max_outlier_error", C.c_float), ("extra_frame_bundle_adjustment_steps", C.c_uint32),
+                ("extra_frame_huber_width", C.c_float), ("extra_frame_search_radius", C.c_float),
+                ("five_point_max_hamming_distance", C.c_int32), ("five_point_min_hamming_difference", C.c_int32),
+                ("extra_frame_max_hamming_distance", C.c_int32), ("extra_frame_min_hamming_difference", C.c_int32)]
+
+    @classmethod
+    def make(cls, **kw):
+        return cls(struct_size=C.sizeof(cls), **kw)
+
+
 class StereoMapInitResultC(C.Structure):
     """mage_stereo_map_init_result (include/mage_hot.h)."""
     _fields_ = [("code", C.c_int32), ("crop", C.c_int32 * 4), ("n_masked", C.c_uint32), ("n_matches", C.c_uint32),
@@ -178,6 +209,14 @@ NP_DTYPE = np.dtype([("position", "<f4", 3), ("mean_view_dir", "<f4", 3), ("d_mi
 # mage_stereo_point (28 B)
 SP_DTYPE = np.dtype([("query_idx", "<i4"), ("train_idx", "<i4"), ("distance", "<f4"), ("position", "<f4", 3),
                      ("near_parallel", "<u4")])
+
+# mage_mono_init_result (408 B)
+MI_RESULT_DTYPE = np.dtype([("verdict", "<u4"), ("status", "<u4"), ("n_matches", "<u4"), ("n_points", "<u4"),
+                            ("win_iteration", "<i4"), ("win_root", "<i4"), ("win_indices", "<i4", 5),
+                            ("win_score", "<f4"), ("selected_pose", "<i4"), ("next_best_score", "<f4"),
+                            ("pos3", "<f4", 6), ("r9", "<f4", 18), ("cand_pos3", "<f4", 12), ("cand_r9", "<f4", 36),
+                            ("cand_score", "<f4", 4), ("cand_median", "<f4", 4), ("cand_count", "<u4", 4),
+                            ("cand_flags", "<u4", 4)])
 
 # mage_new_point_assoc (16 B)
 NA_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("octave", "<i4"), ("keypoint", "<i4")])
@@ -316,6 +355,13 @@ def _declare(L: C.CDLL) -> None:
         vp, vp, vp, vp, vp, vp, vp)
     sig("mage_stereo_init_triangulate", st, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp,
         u32, vp, vp, vp, vp, vp, vp, vp, C.c_int)
+    sig("mage_mono_init_trace_bytes", u64, u32)
+    sig("mage_mono_init_scratch_bytes", u64, u32, u32, i64, i64, i32, i32)
+    sig("mage_mono_init_two_view_batch_device", st, vp, u32, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, u32, vp, vp, vp,
+        u32, vp, vp, vp, vp, vp, vp, vp, vp)
+    sig("mage_mono_init_two_view", st, vp, vp, vp, vp, u32, vp, vp, u32, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp,
+        vp, C.c_int)
+    sig("mage_mono_init_two_view_host", st, vp, vp, vp, u32, vp, u32, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp)
     sig("mage_overlap_crop_source_in_target", st, vp, vp, vp, f32, vp)
     sig("mage_stereo_map_init", st, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp, C.c_int)
     sig("mage_debug_stereo_init_host", st, vp, vp, vp, vp, vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp)

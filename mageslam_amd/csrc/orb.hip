@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "cv_rng.hpp"
 #include "fast_tile_plan.hpp"
 #include "lds_sort.hpp"
 #include "orb_tables.hpp"
@@ -2534,16 +2535,12 @@ mage_status resize_linear_device(const uint8_t* src, int sw, int sh, int sstride
 
 namespace {
 
-// MakeRandomPattern (OpenCVModified.cpp:551-560) with OpenCV 3.4.0's cv::RNG (multiply-with-carry:
-// state = (unsigned)state * 4164903690 + (state >> 32); uniform(a, b) = a + next() % (b - a)),
+// MakeRandomPattern (OpenCVModified.cpp:551-560) with OpenCV 3.4.0's cv::RNG (cv_rng.hpp),
 // seed 0x34985739; stored as (x0, y0, x1, y1) per test like the pre-rotated tables.
 void make_random_pattern(int patch, int8_t out[1024])
 {
-    uint64_t st = 0x34985739u;
-    auto uniform = [&](int a, int b) {
-        st = (uint64_t)(uint32_t)st * 4164903690ull + (st >> 32);
-        return a == b ? a : (int)((uint32_t)st % (uint32_t)(b - a) + (uint32_t)a);
-    };
+    CvRng rng(0x34985739u);
+    auto uniform = [&](int a, int b) { return rng.uniform(a, b); };
     for (int i = 0; i < 512; i++) {
         out[2 * i] = (int8_t)uniform(-patch / 2, patch / 2 + 1);
         out[2 * i + 1] = (int8_t)uniform(-patch / 2, patch / 2 + 1);
