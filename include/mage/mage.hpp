@@ -720,7 +720,24 @@ struct MonoInitializationData {
     std::vector<uint32_t> BundleCameras, BundleMapPoints;
 };
 
-// The two-view stage of MapInitialization (Tracking/MapInitialization.h) over mage_mono_init_two_view.
+// The third frame as LocateThirdFrame leaves it.  The reference keeps the MIDPOINT pose for the frame
+// (MapInitialization.cpp:840) and drops OptimizeCameraPose's result; both are here.
+struct MonoThirdFrame {
+    std::array<float, 3> Position, OptimizedPosition;  // view-space t
+    std::array<float, 9> Rotation, OptimizedRotation;  // column-major R
+    std::vector<int32_t> KeyPointOf;     // per map point: its keypoint in the third frame, or -1
+    std::vector<uint8_t> Verdicts;       // per map point: MAGE_M3_PT_*
+    std::vector<int32_t> Distances;      // per map point: best distance of frame 0's / frame 1's query, or -1
+    std::vector<float> Projections;      // per map point: x, y through the midpoint pose
+    std::vector<uint8_t> Unassociated;   // per third-frame keypoint: 1 = still free after the matching
+    std::vector<float> Observations;     // the surviving associations as bundle-adjustment observations
+    std::vector<uint32_t> ObservationPoints, ObservationCameras;
+    std::vector<float> ObservationInformation;
+    std::vector<uint8_t> Outliers;       // a device ran: the bundle adjustment's flag per matched point
+};
+
+// The two-view stage and the third frame of MapInitialization (Tracking/MapInitialization.h) over
+// mage_mono_init_two_view and mage_mono_init_third_frame.
 class MonoMapInit {
 public:
     // device < 0 runs the CPU backend, which needs the matches.
@@ -788,13 +805,90 @@ public:
         return d;
     }
 
+    // The third frame of TryIntializeMapWithProvidedFrames (MapInitialization.cpp:695-840): the middle
+    // frame at the midpoint pose of the pair, every map point (points: xyz in MapPoints order, with its
+    // keypoint index in frame 0 and frame 1) looked up in it under both descriptor bags, the pose-only
+    // bundle adjustment, the cull and the two gates.  std::nullopt where the reference returns false;
+    // LastThirdResult().verdict then says why (MAGE_M3_*).  The CPU backend (device < 0) has no pose
+    // bundle adjustment: it takes its outcome in `ba` (null stops it after the first gate, and a
+    // frame that passed it is then returned as it stands).  Throws as InitializeWithFrames does.
+    struct ThirdFrameBA {
+        std::vector<uint8_t> Outlier;  // per matched point, in point order
+        std::array<float, 3> Position;
+        std::array<float, 9> Rotation;
+        float MeanSquareError;
+    };
+    std::optional<MonoThirdFrame> LocateThirdFrame(const std::array<float, 6>& positions,
+                                                   const std::array<float, 18>& rotations,
+                                                   const std::vector<float>& points,
+                                                   const std::vector<int32_t>& frame0Index,
+                                                   const std::vector<int32_t>& frame1Index, const uint8_t* descriptors0,
+                                                   uint32_t n0, const uint8_t* descriptors1, uint32_t n1,
+                                                   const MonoFrame& thirdFrame, uint32_t cameraIndex,
+                                                   const ThirdFrameBA* ba = nullptr)
+    {
+        const uint32_t n = (uint32_t)frame0Index.size();
+        if (points.size() != 3 * (size_t)n || frame1Index.size() != n)
+            throw std::invalid_argument("one position and two keypoint indices per map point");
+        if (!thirdFrame.Descriptors && !thirdFrame.KeyPoints->empty())
+            throw std::invalid_argument("the third frame's descriptors are needed");
+        const uint32_t n2 = (uint32_t)thirdFrame.KeyPoints->size();
+        MonoThirdFrame f;
+        f.KeyPointOf.resize(n);
+        f.Verdicts.resize(n);
+        f.Distances.resize(2 * (size_t)n);
+        f.Projections.resize(2 * (size_t)n);
+        f.Unassociated.resize(n2);
+        f.Observations.resize(2 * (size_t)n);
+        f.ObservationPoints.resize(n);
+        f.ObservationCameras.resize(n);
+        f.ObservationInformation.resize(n);
+        f.Outliers.resize(n);
+        m_third = mage_mono_init_third_result{};
+        if (m_device < 0)
+            check(mage_mono_init_third_frame_host(
+                &m_settings, thirdFrame.Intrinsics.data(), positions.data(), rotations.data(), points.data(), n,
+                frame0Index.data(), frame1Index.data(), descriptors0, n0, descriptors1, n1, thirdFrame.KeyPoints->data(),
+                thirdFrame.Descriptors, n2, cameraIndex, ba ? ba->Outlier.data() : nullptr,
+                ba ? ba->Position.data() : nullptr, ba ? ba->Rotation.data() : nullptr, ba ? ba->MeanSquareError : 0.f,
+                &m_third, f.KeyPointOf.data(), f.Verdicts.data(), f.Distances.data(), f.Projections.data(),
+                f.Unassociated.data(), f.Observations.data(), f.ObservationPoints.data(), f.ObservationCameras.data(),
+                f.ObservationInformation.data(), nullptr, nullptr, nullptr));
+        else
+            check(mage_mono_init_third_frame(
+                &m_settings, thirdFrame.Intrinsics.data(), positions.data(), rotations.data(), points.data(), n,
+                frame0Index.data(), frame1Index.data(), descriptors0, n0, descriptors1, n1, thirdFrame.KeyPoints->data(),
+                thirdFrame.Descriptors, n2, cameraIndex, &m_third, f.KeyPointOf.data(), f.Verdicts.data(),
+                f.Distances.data(), f.Projections.data(), f.Unassociated.data(), f.Observations.data(),
+                f.ObservationPoints.data(), f.ObservationCameras.data(), f.ObservationInformation.data(),
+                f.Outliers.data(), m_device));
+        if (m_third.status & MAGE_M3_STATUS_OVER_LIMIT)
+            throw Error(MAGE_EUNSUPPORTED, "more than 4096 map points or third-frame keypoints");
+        if (m_third.status & MAGE_M3_STATUS_BAD_INDEX) throw std::out_of_range("a map point names no keypoint");
+        if (m_third.verdict != MAGE_M3_OK) return std::nullopt;
+        const bool finished = m_device >= 0 || ba;
+        const size_t na = finished ? m_third.n_associated : 0;
+        std::copy(m_third.pos3, m_third.pos3 + 3, f.Position.begin());
+        std::copy(m_third.r9, m_third.r9 + 9, f.Rotation.begin());
+        std::copy(m_third.opt_pos3, m_third.opt_pos3 + 3, f.OptimizedPosition.begin());
+        std::copy(m_third.opt_r9, m_third.opt_r9 + 9, f.OptimizedRotation.begin());
+        f.Observations.resize(2 * na);
+        f.ObservationPoints.resize(na);
+        f.ObservationCameras.resize(na);
+        f.ObservationInformation.resize(na);
+        f.Outliers.resize(m_device >= 0 ? m_third.n_matched : 0);
+        return f;
+    }
+
     const mage_mono_init_result& LastResult() const { return m_last; }
     const std::vector<DMatch>& LastMatches() const { return m_matches; }
+    const mage_mono_init_third_result& LastThirdResult() const { return m_third; }
 
 private:
     mage_mono_init_settings m_settings;
     int m_device;
     mage_mono_init_result m_last{};
+    mage_mono_init_third_result m_third{};
     std::vector<DMatch> m_matches;
 };
 

@@ -803,9 +803,9 @@ mage_status mage_debug_stereo_init_host(const mage_stereo_init_settings* setting
 /* MonoMapInitializationSettings (MageSettings.h:95-128) in the reference's order: its scalars, then
  * its two OrbMatcherSettings bags (FivePointMatchingSettings, ExtraFrameMatchingSettings).
  * struct_size must be sizeof(mage_mono_init_settings); anything else is MAGE_EINVAL.  The two-view
- * stage reads the fields marked (*); the others belong to the rest of
- * TryIntializeMapWithProvidedFrames (new points, the bundle adjustments, the third frame,
- * validation) and are carried for it. */
+ * stage reads the fields marked (*), the third-frame stage (mage_mono_init_third_frame*) those
+ * marked (3); the others belong to the rest of TryIntializeMapWithProvidedFrames (new points, the
+ * bundle adjustments, validation) and are carried for it. */
 typedef struct mage_mono_init_settings {
     uint32_t struct_size;
     float fundamental_transfer_error_threshold;  /* (*) FundamentalTransferErrorThreshold 1.1 */
@@ -814,7 +814,7 @@ typedef struct mage_mono_init_settings {
     float min_inlier_percentage;                 /* (*) MinInlierPercentage 0.5 */
     uint32_t min_initial_map_points;             /* MinInitialMapPoints 40 */
     uint32_t min_map_points;                     /* MinMapPoints 60 */
-    float min_third_frame_match_percentage;      /* MinThirdFrameMatchPercentage 0.5 */
+    float min_third_frame_match_percentage;      /* (3) MinThirdFrameMatchPercentage 0.5 */
     float feature_covisibility_threshold;        /* FeatureCovisibilityThreshold 0.35 */
     float max_parallax_3d_distance;              /* (*) MaxParallax3dDistance 500 */
     float max_parallax_3d_median_distance;       /* (*) MaxParallax3dMedianDistance 20 */
@@ -837,14 +837,14 @@ typedef struct mage_mono_init_settings {
     float final_ba_min_mean_square_error;        /* FinalBA_MinMeanSquareError 0 */
     uint32_t final_ba_num_steps_per_run;         /* FinalBA_NumStepsPerRun 5 */
     uint32_t final_ba_num_steps;                 /* FinalBA_NumSteps 15 */
-    float extra_frame_max_outlier_error;         /* ExtraFrame_MaxOutlierError 8 */
-    uint32_t extra_frame_bundle_adjustment_steps; /* ExtraFrame_BundleAdjustmentSteps 5 */
-    float extra_frame_huber_width;               /* ExtraFrame_HuberWidth 4 */
-    float extra_frame_search_radius;             /* ExtraFrame_SearchRadius 40 */
-    int32_t five_point_max_hamming_distance;     /* (*) FivePointMatchingSettings.MaxHammingDistance 30 */
-    int32_t five_point_min_hamming_difference;   /* (*) FivePointMatchingSettings.MinHammingDifference 1 */
-    int32_t extra_frame_max_hamming_distance;    /* ExtraFrameMatchingSettings.MaxHammingDistance 30 */
-    int32_t extra_frame_min_hamming_difference;  /* ExtraFrameMatchingSettings.MinHammingDifference 1 */
+    float extra_frame_max_outlier_error;         /* (3) ExtraFrame_MaxOutlierError 8 */
+    uint32_t extra_frame_bundle_adjustment_steps; /* (3) ExtraFrame_BundleAdjustmentSteps 5 */
+    float extra_frame_huber_width;               /* (3) ExtraFrame_HuberWidth 4 */
+    float extra_frame_search_radius;             /* (3) ExtraFrame_SearchRadius 40 */
+    int32_t five_point_max_hamming_distance;     /* (*) (3) FivePointMatchingSettings.MaxHammingDistance 30 */
+    int32_t five_point_min_hamming_difference;   /* (*) (3) FivePointMatchingSettings.MinHammingDifference 1 */
+    int32_t extra_frame_max_hamming_distance;    /* (3) ExtraFrameMatchingSettings.MaxHammingDistance 30 */
+    int32_t extra_frame_min_hamming_difference;  /* (3) ExtraFrameMatchingSettings.MinHammingDifference 1 */
 } mage_mono_init_settings;
 
 /* A pair's verdict: InitializeWithFrames' reasons to give up, in its order. */
@@ -949,6 +949,116 @@ mage_status mage_mono_init_two_view_host(const mage_mono_init_settings* settings
                                          mage_mono_init_result* result, mage_stereo_point* out, uint32_t cap,
                                          float* ba_points, float* ba_uv, uint32_t* ba_cam, uint32_t* ba_pt,
                                          float* ba_info, void* trace);
+
+/* The third frame of TryIntializeMapWithProvidedFrames (MapInitialization.cpp:695-840): the middle
+ * frame is placed half way between the initialisation pair, every map point is looked up in it
+ * twice (frame 0's descriptor under ExtraFrameMatchingSettings, frame 1's under
+ * FivePointMatchingSettings) against one shared mask of unassociated keypoints, the better match
+ * takes the keypoint, a pose-only bundle adjustment culls outliers, and two gates on
+ * MinThirdFrameMatchPercentage decide. */
+
+/* A problem's verdict. */
+#define MAGE_M3_OK 0
+#define MAGE_M3_FEW_MATCHES 1    /* too few associations after the matching (:803), or no map points */
+#define MAGE_M3_FEW_AFTER_CULL 2 /* too few left after the outliers were culled (:835) */
+
+/* Bits of a problem's status word. */
+#define MAGE_M3_STATUS_OVER_LIMIT 1u /* over 4096 points or third-frame keypoints, or a count over its pitch / cap */
+#define MAGE_M3_STATUS_BAD_INDEX 2u  /* a point's keypoint index names no keypoint of frame 0 / frame 1 */
+
+/* A point's verdict byte. */
+#define MAGE_M3_PT_BEHIND 0   /* projected behind the midpoint camera (:728): never searched */
+#define MAGE_M3_PT_NO_MATCH 1 /* neither query matched */
+#define MAGE_M3_PT_FRAME0 2   /* took the match of frame 0's descriptor */
+#define MAGE_M3_PT_FRAME1 3   /* took the match of frame 1's descriptor (strictly closer, or the only one) */
+#define MAGE_M3_PT_CULLED 4   /* matched, then culled as an outlier of the pose bundle adjustment (:829-832) */
+
+/* Written whole for every problem; with a status bit set the rest is zero apart from n_points and
+ * nothing else of the problem is written.  Poses as mage_ba_set_cameras takes them.  The reference
+ * keeps the MIDPOINT pose for the frame (:840) and drops the optimised one; both are reported. */
+typedef struct mage_mono_init_third_result {
+    uint32_t verdict;      /* MAGE_M3_* */
+    uint32_t status;       /* MAGE_M3_STATUS_* bits */
+    uint32_t n_points;     /* the map points given */
+    uint32_t n_behind;     /* skipped: Distance < 0 */
+    uint32_t n_matched;    /* associations after the matching */
+    uint32_t n_outliers;   /* culled by the bundle adjustment (0 when it did not run) */
+    uint32_t n_associated; /* n_matched - n_outliers: the observations written */
+    float mean_sq;         /* the bundle adjustment's mean square error (0 when it did not run) */
+    float pos3[3], r9[9];         /* the frame's pose: the midpoint pose */
+    float opt_pos3[3], opt_r9[9]; /* OptimizeCameraPose's result (zero when it did not run) */
+} mage_mono_init_third_result;
+
+/* Bytes of mage_mono_init_third_frame_batch_device's scratch.  offsets: NULL, or 13 words that
+ * receive the byte offsets of its arrays, in this order: obs_start (problems + 1 uint32, the prefix
+ * of ba_count), ba_count (per problem the observations handed to the bundle adjustment: n_matched,
+ * or 0 after a failed first gate), ba_pos3, ba_r9 (its start, the midpoint pose), matched
+ * (problems x cap uint32: the matched points' indices in point order), ba_points (3 floats), ba_uv
+ * (2 floats), ba_info, outlier (uint8) per observation, prefix-packed over the problems, and the
+ * bundle adjustment's opt_pos3, opt_r9, mean_sq and opt_qt7 (its fp64 state, 7 doubles) per problem. */
+uint64_t mage_mono_init_third_scratch_bytes(uint32_t problems, uint32_t cap, uint64_t* offsets);
+
+/* `problems` independent third frames, launches on `stream` with no host step between them: the
+ * match kernel (midpoint pose, projection, both queries per point in order, the first gate), a
+ * scan-and-pack launch, mage_ba_pose_batch_device (ExtraFrame_BundleAdjustmentSteps x
+ * ExtraFrame_HuberWidth, ExtraFrame_MaxOutlierError^2, info = MapPointRefinementConfidence(1)) and
+ * the finish kernel (cull, second gate, compaction).
+ * Per problem: d_intr4 4 floats {cx, cy, fx, fy} of the third frame; d_pos3 6 / d_r9 18 floats, the
+ * poses of frame 0 then frame 1; d_points cap x 3 floats with d_n_points[p] of them used, in
+ * initializationData.MapPoints order; d_idx0 / d_idx1 cap words, each point's keypoint in frame 0 /
+ * frame 1; d_desc0 / d_desc1 the two frames' 32-byte descriptors, pitch0 / pitch1 per problem, counts
+ * d_n0 / d_n1; the third frame's keypoints and descriptors pitch2 per problem, count d_n2 (only its
+ * octave-0 keypoints are candidates: the query octave is 0).  Descriptor pointers 16-byte aligned.
+ * Outputs per problem: d_result; cap words d_keypoint (the point's keypoint in the third frame, -1
+ * when it has none or lost it), cap bytes d_verdict (MAGE_M3_PT_*), 2 x cap words d_dist (the best
+ * distance of query 0 and of query 1 among the candidates the point saw at its turn, -1 when there
+ * was none), 2 x cap floats d_proj (every point's ProjectUndistorted position, behind or not); pitch2
+ * bytes d_mask (1 = still unassociated after the matching; taken keypoints stay
+ * taken when their point is culled, as in the reference); and the surviving associations compacted in
+ * point order as bundle-adjustment observations, n_associated of them: d_obs_uv (2 floats), d_obs_pt
+ * (the point's index), d_obs_cam (cam_index), d_obs_info.  Nothing is written past a problem's
+ * counts.  d_scratch: mage_mono_init_third_scratch_bytes(problems, cap, NULL) bytes, 256-byte
+ * aligned. */
+mage_status mage_mono_init_third_frame_batch_device(
+    const mage_mono_init_settings* settings, uint32_t problems, const float* d_intr4, const float* d_pos3,
+    const float* d_r9, const float* d_points, uint32_t cap, const uint32_t* d_n_points, const int32_t* d_idx0,
+    const int32_t* d_idx1, const uint8_t* d_desc0, int64_t pitch0, const uint32_t* d_n0, const uint8_t* d_desc1,
+    int64_t pitch1, const uint32_t* d_n1, const mage_keypoint* d_kp2, const uint8_t* d_desc2, int64_t pitch2,
+    const uint32_t* d_n2, uint32_t cam_index, mage_mono_init_third_result* d_result, int32_t* d_keypoint,
+    uint8_t* d_verdict, int32_t* d_dist, float* d_proj, uint8_t* d_mask, float* d_obs_uv, uint32_t* d_obs_pt, uint32_t* d_obs_cam,
+    float* d_obs_info, void* d_scratch, mage_stream stream);
+
+/* One problem, host buffers, synchronous, runs on `device`: arrays as one problem of the batched
+ * form with cap = n_points and the pitches equal to the counts.  outlier: NULL, or n_points bytes
+ * that receive the bundle adjustment's flag per matched point, in point order (n_matched of them;
+ * none after a failed first gate). */
+mage_status mage_mono_init_third_frame(const mage_mono_init_settings* settings, const float* intr4, const float* pos3,
+                                       const float* r9, const float* points, uint32_t n_points, const int32_t* idx0,
+                                       const int32_t* idx1, const uint8_t* desc0, uint32_t n0, const uint8_t* desc1,
+                                       uint32_t n1, const mage_keypoint* kp2, const uint8_t* desc2, uint32_t n2,
+                                       uint32_t cam_index, mage_mono_init_third_result* result, int32_t* keypoint,
+                                       uint8_t* verdict, int32_t* dist, float* proj, uint8_t* mask, float* obs_uv,
+                                       uint32_t* obs_pt, uint32_t* obs_cam, float* obs_info, uint8_t* outlier,
+                                       int device);
+
+/* The same in plain C++ on the calling thread: the reference's sequential loop, literally, the CPU
+ * backend; its matching half is bit-identical to the match kernel.  The library has no host pose
+ * bundle adjustment, so its outcome is an input: outlier NULL stops after the first gate (the record
+ * as the match kernel leaves it, no observations written); otherwise n_matched flags in point order
+ * with the optimised pose opt_pos3 / opt_r9 and mean_sq, and the cull, the second gate and the
+ * compaction run (ignored after a failed first gate, where the observations are all the matches).
+ * ba_points / ba_uv / ba_info: NULL, or n_points x 3 / 2 / 1 floats that receive the bundle
+ * adjustment's inputs, n_matched of them.  No GPU. */
+mage_status mage_mono_init_third_frame_host(const mage_mono_init_settings* settings, const float* intr4,
+                                            const float* pos3, const float* r9, const float* points,
+                                            uint32_t n_points, const int32_t* idx0, const int32_t* idx1,
+                                            const uint8_t* desc0, uint32_t n0, const uint8_t* desc1, uint32_t n1,
+                                            const mage_keypoint* kp2, const uint8_t* desc2, uint32_t n2,
+                                            uint32_t cam_index, const uint8_t* outlier, const float* opt_pos3,
+                                            const float* opt_r9, float mean_sq, mage_mono_init_third_result* result,
+                                            int32_t* keypoint, uint8_t* verdict, int32_t* dist, float* proj,
+                                            uint8_t* mask, float* obs_uv, uint32_t* obs_pt, uint32_t* obs_cam,
+                                            float* obs_info, float* ba_points, float* ba_uv, float* ba_info);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Local bundle adjustment — replaces BundlerLib (Dependencies/BundlerLib/Include/BundlerLib.h) */

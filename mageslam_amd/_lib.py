@@ -44,6 +44,8 @@ EXPORTS = [
     "mage_stereo_init_triangulate", "mage_stereo_init_triangulate_batch_device", "mage_stereo_init_triangulate_host",
     "mage_mono_init_trace_bytes", "mage_mono_init_scratch_bytes",
     "mage_mono_init_two_view", "mage_mono_init_two_view_batch_device", "mage_mono_init_two_view_host",
+    "mage_mono_init_third_scratch_bytes", "mage_mono_init_third_frame_batch_device", "mage_mono_init_third_frame",
+    "mage_mono_init_third_frame_host",
 ]
 
 
@@ -218,6 +220,11 @@ MI_RESULT_DTYPE = np.dtype([("verdict", "<u4"), ("status", "<u4"), ("n_matches",
                             ("cand_score", "<f4", 4), ("cand_median", "<f4", 4), ("cand_count", "<u4", 4),
                             ("cand_flags", "<u4", 4)])
 
+# mage_mono_init_third_result (128 B)
+M3_RESULT_DTYPE = np.dtype([("verdict", "<u4"), ("status", "<u4"), ("n_points", "<u4"), ("n_behind", "<u4"),
+                            ("n_matched", "<u4"), ("n_outliers", "<u4"), ("n_associated", "<u4"), ("mean_sq", "<f4"),
+                            ("pos3", "<f4", 3), ("r9", "<f4", 9), ("opt_pos3", "<f4", 3), ("opt_r9", "<f4", 9)])
+
 # mage_new_point_assoc (16 B)
 NA_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("octave", "<i4"), ("keypoint", "<i4")])
 
@@ -362,6 +369,13 @@ def _declare(L: C.CDLL) -> None:
     sig("mage_mono_init_two_view", st, vp, vp, vp, vp, u32, vp, vp, u32, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp,
         vp, C.c_int)
     sig("mage_mono_init_two_view_host", st, vp, vp, vp, u32, vp, u32, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp)
+    sig("mage_mono_init_third_scratch_bytes", u64, u32, u32, vp)
+    sig("mage_mono_init_third_frame_batch_device", st, vp, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp, i64, vp, vp, i64,
+        vp, vp, vp, i64, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp)
+    sig("mage_mono_init_third_frame", st, vp, vp, vp, vp, vp, u32, vp, vp, vp, u32, vp, u32, vp, vp, u32, u32, vp, vp,
+        vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int)
+    sig("mage_mono_init_third_frame_host", st, vp, vp, vp, vp, vp, u32, vp, vp, vp, u32, vp, u32, vp, vp, u32, u32, vp,
+        vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp)
     sig("mage_overlap_crop_source_in_target", st, vp, vp, vp, f32, vp)
     sig("mage_stereo_map_init", st, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp, C.c_int)
     sig("mage_debug_stereo_init_host", st, vp, vp, vp, vp, vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp)

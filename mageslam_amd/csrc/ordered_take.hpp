@@ -176,4 +176,83 @@ __device__ __forceinline__ void resolve_in_order(int count, int max_dist, int mi
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Two queries per item (the third frame of the monocular map initialisation,
+// MapInitialization.cpp:730-799): every item looks its position up twice against the same mask
+// state, each query under its own maxDist / minDiff, and takes the keypoint of the better match —
+// query 1's only when both matched and its distance is strictly smaller, or when it alone matched.
+// The round protocol is resolve_in_order's, and so is the argument: an item's outcome (both queries'
+// results and hence the keypoint it takes) depends on the earlier items only through the keypoints
+// they take out of the union of its two candidate sets.  A lane is therefore in conflict when a
+// lower lane's mark sits on a candidate of EITHER query; a final lane has no earlier lane's mark in
+// that union, all items before the round are committed, and its outcome is the sequential loop's.
+// A lane marks only the one keypoint it would take (the winner's): the loser's match stays in the
+// pool, as in the reference.  Lane r0 never conflicts, so every round commits at least one item.
+// ---------------------------------------------------------------------------------------------
+
+// A kept candidate of a two-query item: t << 18 | d0 << 9 | d1.
+static_assert(OT_TARGET_BITS + 2 * OT_DIST_BITS <= 32, "a two-query kept entry must fit a word");
+__device__ __forceinline__ uint32_t kept_entry2(int t, int d0, int d1)
+{
+    return (uint32_t)t << (2 * OT_DIST_BITS) | (uint32_t)d0 << OT_DIST_BITS | (uint32_t)d1;
+}
+__device__ __forceinline__ int kept_target2(uint32_t v) { return (int)(v >> (2 * OT_DIST_BITS)); }
+__device__ __forceinline__ int kept_dist2(uint32_t v, int q)
+{
+    return (int)(v >> (q ? 0 : OT_DIST_BITS) & ((1u << OT_DIST_BITS) - 1u));
+}
+
+// The in-order take of `count` two-query items by one wave (all 64 lanes call it).  mask, taker: as
+// resolve_in_order.
+//   load(k, act) -> each   as resolve_in_order's, but fn(t, d0, d1) gets the candidate's distance to
+//                  both queries, for every available candidate with d0 <= max_dist[0] or
+//                  d1 <= max_dist[1] (a candidate within neither bound may be visited or not).
+//   commit(k, which, t, best0, best1)   once per item, in the round where it is final: it took t by
+//                  query `which` (0 / 1), or nothing (-1); best0 / best1: each query's best distance
+//                  within its bound under the mask the item saw, or -1.
+template <typename Load, typename Commit>
+__device__ __forceinline__ void resolve_pairs_in_order(int count, const int (&max_dist)[2], const int (&min_diff)[2],
+                                                       uint32_t* mask, int* taker, Load load, Commit commit)
+{
+    const int lane = threadIdx.x & 63;
+    int r0 = 0;
+    while (r0 < count) {
+        const int k = r0 + lane;
+        const bool act = k < count;
+        auto each = load(k, act);
+        uint32_t bk0 = OT_NO_BEST, bk1 = OT_NO_BEST;
+        each([&](int t, int d0, int d1) {
+            if (d0 <= max_dist[0]) bk0 = min(bk0, (uint32_t)d0 << OT_TARGET_BITS | (uint32_t)t);
+            if (d1 <= max_dist[1]) bk1 = min(bk1, (uint32_t)d1 << OT_TARGET_BITS | (uint32_t)t);
+        });
+        const int t0 = (int)(bk0 & (uint32_t)(OT_MAX_TARGETS - 1)), b0 = (int)(bk0 >> OT_TARGET_BITS);
+        const int t1 = (int)(bk1 & (uint32_t)(OT_MAX_TARGETS - 1)), b1 = (int)(bk1 >> OT_TARGET_BITS);
+        int s0 = max_dist[0] + 1, s1 = max_dist[1] + 1;
+        each([&](int t, int d0, int d1) {
+            if (t < t0 && d0 <= max_dist[0]) s0 = min(s0, d0);
+            if (t < t1 && d1 <= max_dist[1]) s1 = min(s1, d1);
+        });
+        const bool ok0 = bk0 != OT_NO_BEST && s0 - b0 > min_diff[0];
+        const bool ok1 = bk1 != OT_NO_BEST && s1 - b1 > min_diff[1];
+        const int which = ok0 && ok1 ? (b1 < b0 ? 1 : 0) : (ok1 ? 1 : (ok0 ? 0 : -1));
+        const int tw = which == 1 ? t1 : t0;
+        if (which >= 0) atomicMin(&taker[tw], lane);
+        wave_sync();
+        bool conflict = false;
+        each([&](int t, int, int) {
+            if (taker[t] < lane) conflict = true;
+        });
+        const uint64_t cb = __ballot(conflict);
+        const int f = cb ? __builtin_ctzll(cb) : 64;
+        if (act && lane < f) {
+            if (which >= 0) mask_clear(mask, tw);
+            commit(k, which, tw, bk0 != OT_NO_BEST ? b0 : -1, bk1 != OT_NO_BEST ? b1 : -1);
+        }
+        wave_sync();
+        if (which >= 0) taker[tw] = OT_NO_TAKER;
+        wave_sync();
+        r0 += f;
+    }
+}
+
 }  // namespace mage
