@@ -125,6 +125,15 @@ __device__ __forceinline__ v4i expand32_fp4(uint32_t w)
     return r;
 }
 
+// Output dword q of expand32_fp4 alone (MAGE_FP4_PIPE_FILL expands in pieces).
+__device__ __forceinline__ int fp4_dword(uint32_t w, int q)
+{
+    const uint32_t E = w & 0x55555555u, O = (w >> 1) & 0x55555555u;
+    const uint32_t xe = (((E >> (8 * q)) & 0xFFu) * 0x00041041u) & 0x01010101u;
+    const uint32_t xo = (((O >> (8 * q)) & 0xFFu) * 0x00041041u) & 0x01010101u;
+    return (int)__builtin_amdgcn_perm(0u, 0xAAA22A22u, xe | (xo << 1));
+}
+
 // Row offset (within a 32-row tile, lane half 0) of accumulator register g of a 32x32 MFMA.
 __host__ __device__ constexpr int acc_row(int g) { return (g & 3) + 8 * (g >> 2); }
 
@@ -575,6 +584,32 @@ constexpr uint32_t NONE16 = 0x80008000u;
 // dependent LDS round trip ahead of a barrier) cost what the VALU they replace did.
 #define MAGE_FP4_LUT 0
 #endif
+#ifndef MAGE_FP4_PIPE
+// 1: software pipeline over the 16 (column tile, row tile) tiles of a stage.  The four MFMAs of tile
+// n + 1 are issued one at a time between quarters of the fold of tile n, onto a second accumulator;
+// the result is first read when the fold of tile n is done.  The pipeline crosses column tiles (a
+// second bf set, read one tile ahead) and drains at the stage barrier.  Behind a ragged column edge
+// the tile issued ahead multiplies the stage's zero fill and is dropped.  The order is held in the
+// source: sched_barrier fences between the pieces, and, because instruction selection orders pure
+// arithmetic by register pressure before those fences exist, an empty asm statement on each piece's
+// results and on each MFMA's B operand and accumulator.  0: the tile loop as the scheduler orders it
+// (all of a row-tile pair's MFMAs, then its folds).  Every A operand stays in registers: 246 VGPRs
+// (256 with the early fill below), no scratch, the same 122,912 B of LDS.  Exact either way.
+// Measured (profiles/r9_match_pipe.md; tools/abl.py, 256 C2 pairs, variants alternated, five runs
+// each), with the early fill: parent 0.2173-0.2206 ms, pipeline 0.2098-0.2126.
+#define MAGE_FP4_PIPE 1
+#endif
+#ifndef MAGE_FP4_PIPE_FILL
+// With the pipeline: the next stage's fill (its buffer was last read before the previous barrier)
+// moves from the end of a stage to its start, in four pieces under the four MFMAs of the stage's
+// first tile, which otherwise run with nothing under them; the fetch for it runs a stage earlier.
+// Same measurement: 0.2150-0.2166 ms without, 0.2098-0.2126 with.  Without the pipeline it has no
+// effect.
+#define MAGE_FP4_PIPE_FILL 1
+#endif
+#define FP4_PIPE_BODY (MAGE_FP4_PIPE != 0)
+#define FP4_PIPE_FILL (MAGE_FP4_PIPE != 0 && MAGE_FP4_PIPE_FILL != 0)
+static_assert(!MAGE_FP4_PIPE || MAGE_FP4_RT == 4, "the pipeline is written for 4 row tiles per wave");
 
 typedef short s16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t pkmax(uint32_t a, uint32_t b)
@@ -611,6 +646,13 @@ __device__ __forceinline__ v16f tile_mfma_k16(const v4i (&a)[4], const v4i (&b)[
         acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, acc, 4, 4, 0, 127 - 11, 0, 127 - 10);
     }
     return acc;
+}
+// One k-step of the same product (MAGE_FP4_PIPE issues them one at a time).
+__device__ __forceinline__ v16f mfma_k16_step(const v4i& a, const v4i& b, const v16f& c)
+{
+    const v8i av = {a[0], a[1], a[2], a[3], 0, 0, 0, 0};
+    const v8i bv = {b[0], b[1], b[2], b[3], 0, 0, 0, 0};
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, c, 4, 4, 0, 127 - 11, 0, 127 - 10);
 }
 
 // A pending column flush (the second LDS atomic needs the first one's return value; it is issued
@@ -667,6 +709,15 @@ __global__ __launch_bounds__(FT) void match_fp4_kernel(const uint8_t* __restrict
 #endif
         return expand32_fp4(w);
     };
+#if FP4_PIPE_FILL
+    // output dword q of the same (the stage fill in pieces, MAGE_FP4_PIPE_FILL)
+    auto fill_dword = [&](uint32_t w, int q) -> int {
+#if MAGE_FP4_LUT
+        if (MAGE_FP4_LUT & 2) return (int)lut[(w >> (8 * q)) & 0xFFu];
+#endif
+        return fp4_dword(w, q);
+    };
+#endif
     // B resident (and MAGE_FP4_LUT's table filled) before the first pass's stage fetches read it
     // (other threads' rows; without this barrier a fetch could read a row not yet written:
     // test_match_random[513-64] caught it)
@@ -733,10 +784,181 @@ __global__ __launch_bounds__(FT) void match_fp4_kernel(const uint8_t* __restrict
         // accumulator bits of the smallest key with d <= maxDist: (124 << 23) | 64 (272 - maxDist)
         const uint32_t gate_bits = (124u << 23) | (uint32_t)(64 * (K16_D - min(max(maxDist, -1), 127)));
         PendingCol16 pc{0, 0, 0, 0, false};
+#if FP4_PIPE_FILL
+        Fetch nxt{};  // fetched a stage before its fill
+        if (FPF < nstages) nxt = fetch(FPF);
+#endif
         for (int st = 0; st < nstages; st++) {
             const int buf = st % FBUF;
+#if !FP4_PIPE_FILL
             Fetch nxt{};
             if (st + FPF < nstages) nxt = fetch(st + FPF);
+#endif
+#if FP4_PIPE_BODY
+            v4i bf[2][4];  // the column tile's B operands, and the next one's
+            v16f acc[2];   // the tile being folded, and the one the matrix pipe is on
+#if FP4_PIPE_FILL
+            {
+                // the next stage's fill first (its buffer was last read before the previous barrier), in
+                // four pieces under the four MFMAs of the stage's first tile
+                static_assert(FCOLS == 2, "two fill columns make the four pieces");
+                int e[FCOLS][4];
+                if (active) {
+#pragma unroll
+                    for (int s = 0; s < 4; s++) bf[0][s] = stage[buf][0][s][lane];
+                }
+#pragma unroll
+                for (int s = 0; s < 4; s++) {
+                    if (active) {
+                        asm volatile("" : "+v"(bf[0][s]));
+                        acc[0] = mfma_k16_step(a[0][s], bf[0][s], s == 0 ? cc : acc[0]);
+                        asm volatile("" : "+v"(acc[0]));
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    const int k = s >> 1, q = 2 * (s & 1);
+                    e[k][q] = fill_dword(nxt.dw[k], q);
+                    e[k][q + 1] = fill_dword(nxt.dw[k], q + 1);
+                    asm volatile("" : "+v"(e[k][q]), "+v"(e[k][q + 1]));
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if (st + FPF < nstages) {
+#pragma unroll
+                    for (int k = 0; k < FCOLS; k++) {
+                        const int fc = fc0 + k * FSC1;
+                        const bool in = (st + FPF) * FSC + fc < nb;
+                        stage[(st + FPF) % FBUF][fc >> 5][fs >> 1][32 * (fs & 1) + (fc & 31)] =
+                            v4i{in ? e[k][0] : 0, in ? e[k][1] : 0, in ? e[k][2] : 0, in ? e[k][3] : 0};
+                    }
+                }
+                if (st + 1 + FPF < nstages) nxt = fetch(st + 1 + FPF);
+            }
+#endif
+            if (active) {
+#if !FP4_PIPE_FILL
+#pragma unroll
+                for (int s = 0; s < 4; s++) bf[0][s] = stage[buf][0][s][lane];
+                acc[0] = tile_mfma_k16(a[0], bf[0], cc);  // the stage's first tile: nothing to run under
+#endif
+                uint32_t c1 = NONE16, c2 = NONE16;
+                bool any = false;
+#pragma unroll
+                for (int t = 0; t < FNT * FRT; t++) {
+                    const int ct = t / FRT, rt = t % FRT, cur = t & 1;
+                    const int nct = (t + 1) / FRT, nrt = (t + 1) % FRT;  // the tile issued under this one
+                    const bool more = t + 1 < FNT * FRT;
+                    const int colbase = st * FSC + ct * 32;
+                    // k-step s of the next tile, and the next column tile's B reads behind one of them
+                    auto issue = [&](int s) {
+                        if (more) {
+                            // the builtin carries no order of its own: the empty statements on its B
+                            // operand and its result hold it between the fences around this call
+                            asm volatile("" : "+v"(bf[nct & 1][s]));
+                            acc[cur ^ 1] = mfma_k16_step(a[nrt][s], bf[nct & 1][s], s == 0 ? cc : acc[cur ^ 1]);
+                            asm volatile("" : "+v"(acc[cur ^ 1]));
+                        }
+                        if (rt == FRT - 2 && s == 1 && ct + 1 < FNT) {
+#pragma unroll
+                            for (int k = 0; k < 4; k++) bf[(ct + 1) & 1][k] = stage[buf][ct + 1][k][lane];
+                        }
+                    };
+                    const v16i av = __builtin_bit_cast(v16i, acc[cur]);
+                    bool hit = true;
+                    if (MAGE_FP4_GATE && gating) {  // the maxDist gate, as in the body below
+                        uint32_t mx = (uint32_t)av[15];
+#pragma unroll
+                        for (int g = 0; g < 15; g += 3)
+                            mx = max(mx, max(max((uint32_t)av[g], (uint32_t)av[g + 1]), (uint32_t)av[g + 2]));
+                        hit = __ballot(mx >= gate_bits) != 0;
+                        g_tiles++;
+                        g_hits += hit ? 1 : 0;
+                    }
+                    if (!hit) {
+#pragma unroll
+                        for (int s = 0; s < 4; s++) issue(s);
+                    } else {
+                        // the fold of the body below in four pieces, one MFMA of the next tile ahead of each
+                        any = true;
+                        uint32_t P[8], h[4], l[4];
+                        auto rowfold = [&](int q) {
+                            r2[rt][q] = pkmax(r2[rt][q], pkmin(r1[rt][q], P[q]));
+                            r1[rt][q] = pkmax(r1[rt][q], P[q]);
+                        };
+                        issue(0);
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int q = 0; q < 8; q++)
+                            P[q] = __builtin_amdgcn_perm((uint32_t)av[2 * q + 1], (uint32_t)av[2 * q], 0x05040100u);
+                        rowfold(0);
+                        rowfold(1);
+                        // a piece's results pass through an empty statement at its end: the fold is pure
+                        // arithmetic, which instruction selection would otherwise order by register pressure
+                        asm volatile("" : "+v"(P[0]), "+v"(P[1]), "+v"(P[2]), "+v"(P[3]), "+v"(P[4]), "+v"(P[5]), "+v"(P[6]), "+v"(P[7]),
+                                     "+v"(r1[rt][0]), "+v"(r2[rt][0]), "+v"(r1[rt][1]), "+v"(r2[rt][1]));
+                        __builtin_amdgcn_sched_barrier(0);
+                        issue(1);
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int q = 2; q < 7; q++) rowfold(q);
+                        asm volatile("" : "+v"(r1[rt][2]), "+v"(r2[rt][2]), "+v"(r1[rt][3]), "+v"(r2[rt][3]), "+v"(r1[rt][4]), "+v"(r2[rt][4]),
+                                     "+v"(r1[rt][5]), "+v"(r2[rt][5]), "+v"(r1[rt][6]), "+v"(r2[rt][6]));
+                        __builtin_amdgcn_sched_barrier(0);
+                        issue(2);
+                        __builtin_amdgcn_sched_barrier(0);
+                        rowfold(7);
+#pragma unroll
+                        for (int q = 0; q < 4; q++) {
+                            h[q] = pkmax(P[2 * q], P[2 * q + 1]);
+                            l[q] = pkmin(P[2 * q], P[2 * q + 1]);
+                        }
+                        uint32_t hh0 = pkmax(h[0], h[1]), hl0 = pkmin(h[0], h[1]);
+                        uint32_t hh1 = pkmax(h[2], h[3]), hl1 = pkmin(h[2], h[3]);
+                        asm volatile("" : "+v"(r1[rt][7]), "+v"(r2[rt][7]), "+v"(l[0]), "+v"(l[1]), "+v"(l[2]), "+v"(l[3]),
+                                     "+v"(hh0), "+v"(hl0), "+v"(hh1), "+v"(hl1));
+                        __builtin_amdgcn_sched_barrier(0);
+                        issue(3);
+                        __builtin_amdgcn_sched_barrier(0);
+                        uint32_t t1 = pkmax(hh0, hh1);
+                        uint32_t t2 = pkmax3(pkmax3(l[0], l[1], l[2]), pkmax3(l[3], hl0, hl1), pkmin(hh0, hh1));
+                        if (rt & 1) {
+                            t1 ^= 0x00200020u;
+                            t2 ^= 0x00200020u;
+                        }
+                        const uint32_t lo = pkmin(c1, t1);
+                        c1 = pkmax(c1, t1);
+                        c2 = pkmax3(lo, c2, t2);
+                        asm volatile("" : "+v"(c1), "+v"(c2));
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    if (rt & 1) {  // one column flush per 64 rows, as below
+                        if (gating && g_tiles >= 64 && 4 * g_hits > g_tiles) gating = false;
+                        if (any) {
+                            const int kg = kadd - 64 * (rt / 2);
+#if !MAGE_FP4_FLUSH_HALVES
+                            {
+                                const uint32_t o1 = (uint32_t)xor32((int)c1, lane), o2 = (uint32_t)xor32((int)c2, lane);
+                                const uint32_t lo = pkmin(c1, o1);
+                                c1 = pkmax(c1, o1);
+                                c2 = pkmax3(lo, c2, o2);
+                            }
+#endif
+                            const int a1 = lo16s(c1), b1 = hi16s(c1);
+                            const int m1 = max(a1, b1), m2 = max(min(a1, b1), max(lo16s(c2), hi16s(c2)));
+                            const int g1 = ((m1 >> 6) << 16) | ((m1 & 63) + kg);
+                            const int g2 = ((m2 >> 6) << 16) | ((m2 & 63) + kg);
+                            if (pc.live) atomicMax(&colM2[pc.j], pc.old > pc.c1 ? pc.c1 : max(pc.old, pc.c2));
+                            pc.j = colbase + (lane & 31);
+                            pc.c1 = g1;
+                            pc.c2 = g2;
+                            pc.live = (MAGE_FP4_FLUSH_HALVES || lane < 32) && pc.j < nb;
+                            pc.old = pc.live ? atomicMax(&colM1[pc.j], g1) : NONE;
+                        }
+                        c1 = c2 = NONE16;
+                        any = false;
+                    }
+                    if (rt == FRT - 1 && colbase + 32 >= nb) break;  // the tile issued ahead is dropped
+                }
+            }
+#else
             if (active) {
 #pragma unroll
                 for (int ct = 0; ct < FNT; ct++) {
@@ -822,7 +1044,10 @@ __global__ __launch_bounds__(FT) void match_fp4_kernel(const uint8_t* __restrict
                     }
                 }
             }
+#endif
+#if !FP4_PIPE_FILL
             if (st + FPF < nstages) fill((st + FPF) % FBUF, st + FPF, nxt);
+#endif
             __syncthreads();
         }
         if (pc.live) atomicMax(&colM2[pc.j], pc.old > pc.c1 ? pc.c1 : max(pc.old, pc.c2));

@@ -8,6 +8,10 @@ the product).
 variant's per-kernel average launch time (the library's dispatch timestamps) and a checksum of the
 keypoints, descriptors and matches, which must agree between variants of the same algorithm.
 MAGE_ABLATE_GATE=<g> forces the FAST candidate gate of every timed batch.
+
+The fp4 matcher's tile pipeline against the parent commit (profiles/r9_match_pipe.md):
+  python tools/abl.py build mageslam_amd/csrc/match.hip parent@HEAD pipe1:MAGE_FP4_PIPE=1 pipe0:MAGE_FP4_PIPE=0
+  python tools/abl.py run parent,pipe1,pipe0
 """
 import ctypes as C
 import hashlib
