@@ -892,6 +892,112 @@ private:
     std::vector<DMatch> m_matches;
 };
 
+// RelocalizationSettings (MageSettings.h:236-250) with its OrbMatcherSettings bag.
+struct RelocalizationSettings {
+    unsigned MinBruteForceCorrespondences{20}, MinRadiusMatchCorrespondences{15}, MinMapPoints{10};
+    float RansacInliersPctRequired{0.4f}, BundleAdjustInliersPctRequired{0.4f}, RansacConfidence{0.6f};
+    unsigned RoundRobinIterations{5}, RansacIterations{2}, BundleAdjustIterations{10};
+    float SearchRadius{20.0f}, MaxBundleAdjustReprojectionError{8.0f}, MaxBundlePnPReprojectionError{8.0f};
+    struct {
+        int MaxHammingDistance{30}, MinHammingDifference{1};
+    } OrbMatcherSettings;
+
+    mage_reloc_settings ToC() const
+    {
+        mage_reloc_settings s{};
+        s.struct_size = (uint32_t)sizeof(s);
+        s.min_brute_force_correspondences = MinBruteForceCorrespondences;
+        s.min_radius_match_correspondences = MinRadiusMatchCorrespondences;
+        s.min_map_points = MinMapPoints;
+        s.ransac_inliers_pct_required = RansacInliersPctRequired;
+        s.bundle_adjust_inliers_pct_required = BundleAdjustInliersPctRequired;
+        s.ransac_confidence = RansacConfidence;
+        s.round_robin_iterations = RoundRobinIterations;
+        s.ransac_iterations = RansacIterations;
+        s.bundle_adjust_iterations = BundleAdjustIterations;
+        s.search_radius = SearchRadius;
+        s.max_bundle_adjust_reprojection_error = MaxBundleAdjustReprojectionError;
+        s.max_bundle_pnp_reprojection_error = MaxBundlePnPReprojectionError;
+        s.max_hamming_distance = OrbMatcherSettings.MaxHammingDistance;
+        s.min_hamming_difference = OrbMatcherSettings.MinHammingDifference;
+        return s;
+    }
+};
+
+// A pose as the bundle adjustment takes it: view-space t and column-major R.
+struct ViewPose {
+    std::array<float, 3> Position{0.f, 0.f, 0.f};
+    std::array<float, 9> Rotation{1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+};
+
+// The pose-from-nothing stage of PoseEstimator (Tracking/PoseEstimator.h) over mage_reloc_pnp.
+class PoseEstimator {
+public:
+    // device < 0 runs the CPU backend.
+    explicit PoseEstimator(const RelocalizationSettings& settings, int device = 0)
+        : m_settings(settings.ToC()), m_device(device)
+    {
+    }
+
+    // PNPRansac (PoseEstimator.cpp:610-638) with the reference's arguments: calibration {cx, cy, fx,
+    // fy} (undistorted), points3d[i] seen at points2d[i].  useExtrinsicGuess is accepted and ignored,
+    // as OpenCV's RANSAC kernel ignores it.  false where the reference returns false (fewer than
+    // five points, or no hypothesis with five inliers); else `pose` is the winning hypothesis and
+    // `inliers` its inliers in point order WITHOUT those behind the camera — the caller's next step
+    // (RemoveMapPointsThatAreBehind, :338) folded in; LastResult().n_inliers counts them all.
+    // Throws Error (MAGE_EUNSUPPORTED) for more than 4096 points.
+    bool PNPRansac(const std::array<float, 4>& calibration, const std::vector<std::array<float, 3>>& points3d,
+                   const std::vector<std::array<float, 2>>& points2d, bool useExtrinsicGuess, float maxReprojectionError,
+                   float ransacConfidence, unsigned numIterations, ViewPose& pose, std::vector<int>& inliers)
+    {
+        (void)useExtrinsicGuess;
+        if (points3d.size() != points2d.size()) throw std::invalid_argument("one 2D point per 3D point");
+        const uint32_t n = (uint32_t)points3d.size();
+        mage_reloc_settings s = m_settings;
+        s.min_brute_force_correspondences = 0;  // the gates around PNPRansac are the caller's
+        s.ransac_inliers_pct_required = 0.f;
+        s.max_bundle_pnp_reprojection_error = maxReprojectionError;
+        s.ransac_confidence = ransacConfidence;
+        s.ransac_iterations = numIterations;
+        std::vector<float> map(4 * (size_t)n);
+        std::vector<KeyPoint> kp(n);
+        std::vector<DMatch> mm(n);
+        for (uint32_t i = 0; i < n; i++) {
+            std::copy(points3d[i].begin(), points3d[i].end(), &map[4 * (size_t)i]);
+            map[4 * (size_t)i + 3] = 1.f;
+            kp[i] = KeyPoint{};
+            kp[i].x = points2d[i][0];
+            kp[i].y = points2d[i][1];
+            mm[i] = DMatch{};
+            mm[i].query_idx = mm[i].train_idx = (int32_t)i;
+        }
+        const uint32_t cap = std::max<uint32_t>(n, 1);
+        std::vector<uint32_t> idx(cap);
+        std::vector<float> p3(3 * (size_t)cap), uv(2 * (size_t)cap), info(cap);
+        m_last = mage_reloc_pnp_result{};
+        if (m_device < 0)
+            check(mage_reloc_pnp_host(&s, calibration.data(), map.data(), n, kp.data(), n, mm.data(), n, &m_last, idx.data(),
+                                      cap, p3.data(), uv.data(), info.data(), nullptr));
+        else
+            check(mage_reloc_pnp(&s, calibration.data(), map.data(), n, kp.data(), n, mm.data(), n, &m_last, idx.data(),
+                                 cap, p3.data(), uv.data(), info.data(), nullptr, m_device));
+        if (m_last.status & MAGE_RP_STATUS_OVER_LIMIT) throw Error(MAGE_EUNSUPPORTED, "more than 4096 points");
+        inliers.clear();
+        if (m_last.verdict != MAGE_RP_OK) return false;
+        std::copy(m_last.pos3, m_last.pos3 + 3, pose.Position.begin());
+        std::copy(m_last.r9, m_last.r9 + 9, pose.Rotation.begin());
+        inliers.assign(idx.begin(), idx.begin() + m_last.n_kept);
+        return true;
+    }
+
+    const mage_reloc_pnp_result& LastResult() const { return m_last; }
+
+private:
+    mage_reloc_settings m_settings;
+    int m_device;
+    mage_reloc_pnp_result m_last{};
+};
+
 struct BundlerParameters {
     bool ArePointsFixed{false};
 };

@@ -1061,6 +1061,132 @@ mage_status mage_mono_init_third_frame_host(const mage_mono_init_settings* setti
                                             float* obs_info, float* ba_points, float* ba_uv, float* ba_info);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Relocalisation — PoseEstimator::PNPRansac (Core/.../Tracking/PoseEstimator.cpp:610-638) as   */
+/* TryEstimatePoseFromCandidates uses it (:219-437): a pose from 2D-3D matches with no prior   */
+/* ------------------------------------------------------------------------------------------ */
+
+/* RelocalizationSettings (MageSettings.h:236-250) in the reference's order, then its
+ * OrbMatcherSettings bag.  struct_size must be sizeof(mage_reloc_settings); anything else is
+ * MAGE_EINVAL.  The PnP stage reads the fields marked (*); the others belong to the rest of
+ * TryEstimatePoseFromCandidates (the bundle adjustments, the guided search) and are carried for it. */
+typedef struct mage_reloc_settings {
+    uint32_t struct_size;
+    uint32_t min_brute_force_correspondences;   /* (*) MinBruteForceCorrespondences 20 */
+    uint32_t min_radius_match_correspondences;  /* MinRadiusMatchCorrespondences 15 */
+    uint32_t min_map_points;                    /* MinMapPoints 10 */
+    float ransac_inliers_pct_required;          /* (*) RansacInliersPctRequired 0.4 */
+    float bundle_adjust_inliers_pct_required;   /* BundleAdjustInliersPctRequired 0.4 */
+    float ransac_confidence;                    /* (*) RansacConfidence 0.6, in (0, 1) exclusive */
+    uint32_t round_robin_iterations;            /* RoundRobinIterations 5 */
+    uint32_t ransac_iterations;                 /* (*) RansacIterations 2, in 1..256 */
+    uint32_t bundle_adjust_iterations;          /* BundleAdjustIterations 10 */
+    float search_radius;                        /* SearchRadius 20 */
+    float max_bundle_adjust_reprojection_error; /* MaxBundleAdjustReprojectionError 8 */
+    float max_bundle_pnp_reprojection_error;    /* (*) MaxBundlePnPReprojectionError 8 */
+    int32_t max_hamming_distance;               /* OrbMatcherSettings.MaxHammingDistance 30 */
+    int32_t min_hamming_difference;             /* OrbMatcherSettings.MinHammingDifference 1 */
+} mage_reloc_settings;
+
+/* A problem's verdict. */
+#define MAGE_RP_OK 0
+#define MAGE_RP_FEW_MATCHES 1 /* fewer than MinBruteForceCorrespondences matches (:291) */
+#define MAGE_RP_NO_MODEL 2    /* PNPRansac returned false (:319-324): under five matches, or no hypothesis with five inliers */
+#define MAGE_RP_FEW_INLIERS 3 /* inFront / matches < RansacInliersPctRequired (:339); the candidate stays worthwhile */
+
+/* Bits of a problem's status word. */
+#define MAGE_RP_STATUS_OVER_LIMIT 1u /* over 4096 matches or over match_cap, or more keypoints than kp_pitch */
+#define MAGE_RP_STATUS_OVER_CAP 2u   /* more kept inliers than `cap` (n_kept reports cap) */
+#define MAGE_RP_STATUS_BAD_INDEX 4u  /* a match names no keypoint, or a candidate keypoint with no map point */
+
+/* What the stage decides for one problem; written whole for every problem, zero (indices -1, the
+ * pose the identity) where a step was not reached.  The pose is as mage_ba_pose_batch takes it:
+ * view-space t and column-major R, the winning hypothesis's fp64 model rounded to float. */
+typedef struct mage_reloc_pnp_result {
+    uint32_t verdict;       /* MAGE_RP_* */
+    uint32_t status;        /* MAGE_RP_STATUS_* bits; with OVER_LIMIT or BAD_INDEX the problem has no other output */
+    uint32_t n_matches;     /* the matches the stage ran on */
+    uint32_t n_inliers;     /* the winner's inliers (maxGoodCount) */
+    uint32_t n_in_front;    /* those RemoveMapPointsThatAreBehind leaves */
+    uint32_t n_kept;        /* min(n_in_front, cap): the inlier indices written; the observations when OK */
+    int32_t win_iteration;  /* the winner's RANSAC iteration, or -1 */
+    int32_t win_indices[5]; /* its five matches in draw order */
+    uint32_t iterations;    /* the final niters of the adaptive loop */
+    uint32_t iterations_run; /* iterations the loop went through before it ended */
+    float pos3[3], r9[9];
+} mage_reloc_pnp_result;
+
+/* Bytes of one problem's trace for `iterations` RANSAC iterations, arrays in this order:
+ *   double R[iterations][9]      the hypothesis's rotation, row-major (zero without a model);
+ *   double t[iterations][3]      its translation;
+ *   double err[iterations][3]    the three EPnP starts' summed reprojection errors, -1 where a start failed;
+ *   int32 indices[iterations][5] the sample's matches in draw order, or -1 five times (no sample);
+ *   int32 solved[iterations]     1 when the sample gave a model;
+ *   uint32 inliers[iterations]   its inlier count;
+ * 148 bytes per iteration, the total rounded up to 8.  Every iteration is filled, also those the
+ * adaptive loop did not reach.  With exactly five matches iteration 0 is the one solve on all of
+ * them and the others hold no sample. */
+uint64_t mage_reloc_pnp_trace_bytes(uint32_t iterations);
+
+/* Bytes of mage_reloc_pnp_batch_device's scratch: the work buffer (problems traces, when no trace
+ * is given), the gathered correspondences, one bit per match and hypothesis, the kept counts. */
+uint64_t mage_reloc_pnp_scratch_bytes(uint32_t iterations, uint32_t problems, uint32_t match_cap, int32_t with_trace);
+
+/* The PnP stage for `problems` (lost frame, candidate keyframe) problems, five launches on `stream`
+ * with no host step between them:
+ *   a. the limits and index checks, the MinBruteForceCorrespondences gate (:291), the
+ *      correspondences gathered in match order (:301-308), the RANSAC sampler
+ *      (RANSACPointSetRegistrator::getSubset);
+ *   b. EPnP on five points per hypothesis;
+ *   c. the inlier rule of every hypothesis over all matches;
+ *   d. the adaptive loop replayed over the counts, the winner's inliers in match order,
+ *      RemoveMapPointsThatAreBehind (:209-216), the RansacInliersPctRequired gate (:339), the result;
+ *   e. d_obs_start (problems + 1 words, the prefix of the OK problems' kept counts) and the inputs of
+ *      BundleAdjustPose as mage_ba_pose_batch_device takes them, compacted: per kept inlier the map
+ *      point (d_points3), the keypoint (d_uv) and the map point's information value (d_info).
+ * Per problem: d_intr4 4 floats {cx, cy, fx, fy} (the undistorted calibration); d_map_xyzi kf_pitch
+ * x 4 floats, the candidate keyframe's keypoints' map points {x, y, z, information}, information
+ * <= 0 marking a keypoint with no map point; d_kp kp_pitch keypoints of the current frame, d_n_kp
+ * of them valid; d_matches match_cap records, d_n_matches of them valid, query_idx into the
+ * candidate and train_idx into the current frame.  Outputs per problem: d_result; d_inlier_idx cap
+ * match indices (n_kept written, for MAGE_RP_OK and MAGE_RP_FEW_INLIERS); d_pos3 / d_r9 the result's
+ * pose (the identity unless a model was found).  d_points3 / d_uv / d_info hold problems x cap
+ * entries at most.  d_trace: NULL, or problems x mage_reloc_pnp_trace_bytes(iterations) bytes.
+ * d_scratch: mage_reloc_pnp_scratch_bytes(...) bytes, 256-byte aligned.  Nothing is written past a
+ * problem's counts; a problem that stops in (a) leaves its trace untouched; the other problems are
+ * unaffected.  mage_ba_pose_batch_device can be queued behind the stage on the same stream. */
+mage_status mage_reloc_pnp_batch_device(const mage_reloc_settings* settings, uint32_t problems, const float* d_intr4,
+                                        const float* d_map_xyzi, int64_t kf_pitch, const mage_keypoint* d_kp,
+                                        int64_t kp_pitch, const uint32_t* d_n_kp, const mage_dmatch* d_matches,
+                                        uint32_t match_cap, const uint32_t* d_n_matches, mage_reloc_pnp_result* d_result,
+                                        uint32_t* d_inlier_idx, uint32_t cap, uint32_t* d_obs_start, float* d_points3,
+                                        float* d_uv, float* d_info, float* d_pos3, float* d_r9, void* d_trace,
+                                        void* d_scratch, mage_stream stream);
+
+/* One problem, host buffers, synchronous, runs on `device`: map_xyzi n_kf x 4 floats, kp n_kp
+ * keypoints; inlier_idx, points3, uv, info sized for cap entries (n_kept are written, the last three
+ * for MAGE_RP_OK only); trace NULL or mage_reloc_pnp_trace_bytes(iterations) bytes. */
+mage_status mage_reloc_pnp(const mage_reloc_settings* settings, const float* intr4, const float* map_xyzi, uint32_t n_kf,
+                           const mage_keypoint* kp, uint32_t n_kp, const mage_dmatch* matches, uint32_t n_matches,
+                           mage_reloc_pnp_result* result, uint32_t* inlier_idx, uint32_t cap, float* points3, float* uv,
+                           float* info, void* trace, int device);
+
+/* The same in plain C++ on the calling thread: the sequential loop of
+ * RANSACPointSetRegistrator::run over the same arithmetic, the CPU backend, bit-identical to the
+ * kernels.  Without a trace the hypotheses past the loop's end are not computed.  No GPU. */
+mage_status mage_reloc_pnp_host(const mage_reloc_settings* settings, const float* intr4, const float* map_xyzi,
+                                uint32_t n_kf, const mage_keypoint* kp, uint32_t n_kp, const mage_dmatch* matches,
+                                uint32_t n_matches, mage_reloc_pnp_result* result, uint32_t* inlier_idx, uint32_t cap,
+                                float* points3, float* uv, float* info, void* trace);
+
+/* Test hooks of the adaptive loop.  _update: out[g] = RANSACUpdateNumIters(confidence, (n - g) / n,
+ * 5, max_iters) for g in 0..n.  _loop: the loop over given outcomes (solved[i], inliers[i];
+ * every iteration sampled) for n matches, with the replay the kernels run (sequential == 0) or the
+ * twin's sequential loop; out = {winner or -1, its count, final niters, iterations run}. */
+mage_status mage_debug_reloc_pnp_update(double confidence, uint32_t n, uint32_t max_iters, int32_t* out);
+mage_status mage_debug_reloc_pnp_loop(const int32_t* solved, const uint32_t* inliers, uint32_t max_iters, uint32_t n,
+                                      double confidence, int32_t sequential, int32_t* out);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Local bundle adjustment — replaces BundlerLib (Dependencies/BundlerLib/Include/BundlerLib.h) */
 /* ------------------------------------------------------------------------------------------ */
 

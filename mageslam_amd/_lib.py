@@ -46,6 +46,8 @@ EXPORTS = [
     "mage_mono_init_two_view", "mage_mono_init_two_view_batch_device", "mage_mono_init_two_view_host",
     "mage_mono_init_third_scratch_bytes", "mage_mono_init_third_frame_batch_device", "mage_mono_init_third_frame",
     "mage_mono_init_third_frame_host",
+    "mage_reloc_pnp_trace_bytes", "mage_reloc_pnp_scratch_bytes", "mage_reloc_pnp_batch_device", "mage_reloc_pnp",
+    "mage_reloc_pnp_host", "mage_debug_reloc_pnp_update", "mage_debug_reloc_pnp_loop",
 ]
 
 
@@ -188,6 +190,22 @@ class MonoInitSettingsC(C.Structure):
         return cls(struct_size=C.sizeof(cls), **kw)
 
 
+class RelocSettingsC(C.Structure):
+    """mage_reloc_settings (include/mage_hot.h); struct_size is filled in by make()."""
+    _fields_ = [("struct_size", C.c_uint32), ("min_brute_force_correspondences", C.c_uint32),
+                ("min_radius_match_correspondences", C.c_uint32), ("min_map_points", C.c_uint32),
+                ("ransac_inliers_pct_required", C.c_float), ("bundle_adjust_inliers_pct_required", C.c_float),
+                ("ransac_confidence", C.c_float), ("round_robin_iterations", C.c_uint32),
+                ("ransac_iterations", C.c_uint32), ("bundle_adjust_iterations", C.c_uint32),
+                ("search_radius", C.c_float), ("max_bundle_adjust_reprojection_error", C.c_float),
+                ("max_bundle_pnp_reprojection_error", C.c_float), ("max_hamming_distance", C.c_int32),
+                ("min_hamming_difference", C.c_int32)]
+
+    @classmethod
+    def make(cls, **kw):
+        return cls(struct_size=C.sizeof(cls), **kw)
+
+
 class StereoMapInitResultC(C.Structure):
     """mage_stereo_map_init_result (include/mage_hot.h)."""
     _fields_ = [("code", C.c_int32), ("crop", C.c_int32 * 4), ("n_masked", C.c_uint32), ("n_matches", C.c_uint32),
@@ -224,6 +242,12 @@ MI_RESULT_DTYPE = np.dtype([("verdict", "<u4"), ("status", "<u4"), ("n_matches",
 M3_RESULT_DTYPE = np.dtype([("verdict", "<u4"), ("status", "<u4"), ("n_points", "<u4"), ("n_behind", "<u4"),
                             ("n_matched", "<u4"), ("n_outliers", "<u4"), ("n_associated", "<u4"), ("mean_sq", "<f4"),
                             ("pos3", "<f4", 3), ("r9", "<f4", 9), ("opt_pos3", "<f4", 3), ("opt_r9", "<f4", 9)])
+
+# mage_reloc_pnp_result (104 B)
+RP_RESULT_DTYPE = np.dtype([("verdict", "<u4"), ("status", "<u4"), ("n_matches", "<u4"), ("n_inliers", "<u4"),
+                            ("n_in_front", "<u4"), ("n_kept", "<u4"), ("win_iteration", "<i4"),
+                            ("win_indices", "<i4", 5), ("iterations", "<u4"), ("iterations_run", "<u4"),
+                            ("pos3", "<f4", 3), ("r9", "<f4", 9)])
 
 # mage_new_point_assoc (16 B)
 NA_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("octave", "<i4"), ("keypoint", "<i4")])
@@ -376,6 +400,14 @@ def _declare(L: C.CDLL) -> None:
         vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int)
     sig("mage_mono_init_third_frame_host", st, vp, vp, vp, vp, vp, u32, vp, vp, vp, u32, vp, u32, vp, vp, u32, u32, vp,
         vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp)
+    sig("mage_reloc_pnp_trace_bytes", u64, u32)
+    sig("mage_reloc_pnp_scratch_bytes", u64, u32, u32, u32, i32)
+    sig("mage_reloc_pnp_batch_device", st, vp, u32, vp, vp, i64, vp, i64, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp,
+        vp, vp, vp, vp, vp)
+    sig("mage_reloc_pnp", st, vp, vp, vp, u32, vp, u32, vp, u32, vp, vp, u32, vp, vp, vp, vp, C.c_int)
+    sig("mage_reloc_pnp_host", st, vp, vp, vp, u32, vp, u32, vp, u32, vp, vp, u32, vp, vp, vp, vp)
+    sig("mage_debug_reloc_pnp_update", st, f64, u32, u32, vp)
+    sig("mage_debug_reloc_pnp_loop", st, vp, vp, u32, u32, f64, i32, vp)
     sig("mage_overlap_crop_source_in_target", st, vp, vp, vp, f32, vp)
     sig("mage_stereo_map_init", st, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp, C.c_int)
     sig("mage_debug_stereo_init_host", st, vp, vp, vp, vp, vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp)
