@@ -930,7 +930,8 @@ struct ViewPose {
     std::array<float, 9> Rotation{1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
 };
 
-// The pose-from-nothing stage of PoseEstimator (Tracking/PoseEstimator.h) over mage_reloc_pnp.
+// The relocalisation of PoseEstimator (Tracking/PoseEstimator.h): PNPRansac over mage_reloc_pnp and
+// TryEstimatePoseFromCandidates over mage_reloc_guided.
 class PoseEstimator {
 public:
     // device < 0 runs the CPU backend.
@@ -992,10 +993,139 @@ public:
 
     const mage_reloc_pnp_result& LastResult() const { return m_last; }
 
+    // A candidate keyframe as TryEstimatePoseFromCandidates reads it: per keypoint its map point
+    // {x, y, z, information} (information <= 0: not associated), the keypoints and descriptors;
+    // Order empty, or the associated keypoints in IterateAssociations' order; Intrinsics {cx, cy, fx,
+    // fy} of the candidate for the bundle adjustments, all zero = the frame's.
+    struct Candidate {
+        std::vector<std::array<float, 4>> MapPoints;
+        std::vector<KeyPoint> KeyPoints;
+        std::vector<Descriptor> Descriptors;
+        std::vector<int32_t> Order;
+        std::array<float, 4> Intrinsics{0.f, 0.f, 0.f, 0.f};
+    };
+    // keyframe->AddAssociation(mapPoint, index) (:429-430): the candidate's keypoint whose map point
+    // it is, and the frame's keypoint.
+    struct Association {
+        int32_t CandidateKeypoint, FrameKeypoint;
+    };
+
+    // TryEstimatePoseFromCandidates (PoseEstimator.cpp:219-437) behind IndexedMatch, whose matches
+    // per candidate are given (queryIdx into the candidate, trainIdx into the frame): PNPRansac, the
+    // first BundleAdjustPose, the guided search, the second BundleAdjustPose and the gates, for
+    // every candidate on the GPU in one call.  Returns indexOfSuccess, the lowest candidate whose
+    // pass succeeds (what the reference's round-robin returns, every round repeating the same
+    // RANSAC), or -1; on success `pose` is the frame's pose and `associations` what it adds.
+    // poseMaxHammingDist / poseMinHammingDifference are PoseEstimationSettings.OrbMatcherSettings.
+    // Throws Error (MAGE_EUNSUPPORTED) on the CPU backend: the library has no host pose bundle
+    // adjustment (mage_reloc_guided_host takes its outcome as an input).
+    int TryEstimatePoseFromCandidates(const std::array<float, 4>& calibration, const std::vector<Candidate>& candidates,
+                                      const std::vector<std::vector<DMatch>>& matches,
+                                      const std::vector<KeyPoint>& keypoints, const std::vector<Descriptor>& descriptors,
+                                      ViewPose& pose, std::vector<Association>& associations, int poseMaxHammingDist = 30,
+                                      int poseMinHammingDifference = 1)
+    {
+        if (m_device < 0) throw Error(MAGE_EUNSUPPORTED, "TryEstimatePoseFromCandidates needs a GPU device");
+        if (matches.size() != candidates.size()) throw std::invalid_argument("one match list per candidate");
+        if (descriptors.size() != keypoints.size()) throw std::invalid_argument("one descriptor per keypoint");
+        const uint32_t P = (uint32_t)candidates.size();
+        associations.clear();
+        m_guided.clear();
+        m_frame = mage_reloc_frame_result{};
+        m_frame.index = -1;
+        if (P == 0) return -1;
+        size_t pitch = 1, mcap = 1;
+        bool ordered = false;
+        for (uint32_t c = 0; c < P; c++) {
+            const Candidate& k = candidates[c];
+            if (k.KeyPoints.size() != k.MapPoints.size() || k.Descriptors.size() != k.MapPoints.size())
+                throw std::invalid_argument("one map point slot and one descriptor per candidate keypoint");
+            pitch = std::max({pitch, k.MapPoints.size(), k.Order.size()});
+            mcap = std::max(mcap, matches[c].size());
+            ordered = ordered || !k.Order.empty();
+        }
+        std::vector<float> map(4 * pitch * P, 0.f), bai(4 * (size_t)P);
+        std::vector<KeyPoint> kfkp(pitch * P, KeyPoint{});
+        std::vector<uint8_t> kfd(32 * pitch * P, 0);
+        std::vector<int32_t> order(pitch * P, 0);
+        std::vector<uint32_t> nkf(P), nord(P), nm(P);
+        std::vector<DMatch> mm(mcap * P, DMatch{});
+        for (uint32_t c = 0; c < P; c++) {
+            const Candidate& k = candidates[c];
+            const size_t n = k.MapPoints.size();
+            nkf[c] = (uint32_t)n;
+            for (size_t i = 0; i < n; i++) {
+                std::copy(k.MapPoints[i].begin(), k.MapPoints[i].end(), &map[4 * (pitch * c + i)]);
+                std::copy(k.Descriptors[i].begin(), k.Descriptors[i].end(), &kfd[32 * (pitch * c + i)]);
+            }
+            std::copy(k.KeyPoints.begin(), k.KeyPoints.end(), kfkp.begin() + pitch * c);
+            // one order list needs them all: the default order is ascending keypoint index
+            uint32_t no = 0;
+            if (!k.Order.empty())
+                for (int32_t v : k.Order) order[pitch * c + no++] = v;
+            else
+                for (size_t i = 0; i < n; i++)
+                    if (k.MapPoints[i][3] > 0.f) order[pitch * c + no++] = (int32_t)i;
+            nord[c] = no;
+            const bool own = k.Intrinsics[2] != 0.f || k.Intrinsics[3] != 0.f;
+            std::copy(own ? k.Intrinsics.begin() : calibration.begin(), own ? k.Intrinsics.end() : calibration.end(),
+                      &bai[4 * (size_t)c]);
+            nm[c] = (uint32_t)matches[c].size();
+            std::copy(matches[c].begin(), matches[c].end(), mm.begin() + mcap * c);
+        }
+        const uint32_t cap = (uint32_t)pitch;
+        m_guided.assign(P, mage_reloc_guided_result{});
+        m_pnp.assign(P, mage_reloc_pnp_result{});
+        std::vector<int32_t> assoc(2 * (size_t)cap * P);
+        check(mage_reloc_guided(&m_settings, poseMaxHammingDist, poseMinHammingDifference, P, calibration.data(), bai.data(),
+                                map.data(), kfkp.data(), kfd.data(), (uint32_t)pitch, nkf.data(),
+                                ordered ? order.data() : nullptr, ordered ? nord.data() : nullptr,
+                                keypoints.empty() ? nullptr : keypoints.data(),
+                                descriptors.empty() ? nullptr : descriptors.front().data(), (uint32_t)keypoints.size(),
+                                mm.data(), (uint32_t)mcap, nm.data(), cap, m_guided.data(), m_pnp.data(), &m_frame,
+                                assoc.data(), m_device));
+        if (m_frame.index < 0) return -1;
+        std::copy(m_frame.pos3, m_frame.pos3 + 3, pose.Position.begin());
+        std::copy(m_frame.r9, m_frame.r9 + 9, pose.Rotation.begin());
+        const int32_t* a = &assoc[2 * (size_t)cap * (size_t)m_frame.index];
+        for (uint32_t i = 0; i < m_frame.n_assoc; i++) associations.push_back(Association{a[2 * i], a[2 * i + 1]});
+        return m_frame.index;
+    }
+
+    // The same from the vocabulary tree: IndexedMatch of every candidate's associated keypoints
+    // against the frame with the relocaliser's OrbMatcherSettings (:279-289), then the call above.
+    int TryEstimatePoseFromCandidates(const OnlineBowTree& bagOfWords, const std::array<float, 4>& calibration,
+                                      const std::vector<Candidate>& candidates, const std::vector<KeyPoint>& keypoints,
+                                      const std::vector<Descriptor>& descriptors, ViewPose& pose,
+                                      std::vector<Association>& associations, int poseMaxHammingDist = 30,
+                                      int poseMinHammingDifference = 1)
+    {
+        std::vector<std::vector<DMatch>> matches(candidates.size());
+        for (size_t c = 0; c < candidates.size(); c++) {
+            const Candidate& k = candidates[c];
+            if (k.Descriptors.empty() || descriptors.empty() || k.Descriptors.size() > 4096 || descriptors.size() > 4096)
+                continue;  // no match; a side over the limit is reported by the stage
+            std::vector<bool> mask(k.MapPoints.size());
+            for (size_t i = 0; i < mask.size(); i++) mask[i] = k.MapPoints[i][3] > 0.f;
+            IndexedMatch(bagOfWords, k.Descriptors, descriptors, mask, std::vector<bool>(), m_settings.max_hamming_distance,
+                         m_settings.min_hamming_difference, matches[c]);
+        }
+        return TryEstimatePoseFromCandidates(calibration, candidates, matches, keypoints, descriptors, pose, associations,
+                                             poseMaxHammingDist, poseMinHammingDifference);
+    }
+
+    // Per candidate of the last call: the guided half's record and the PnP stage's.
+    const std::vector<mage_reloc_guided_result>& LastCandidates() const { return m_guided; }
+    const std::vector<mage_reloc_pnp_result>& LastCandidatesPnP() const { return m_pnp; }
+    const mage_reloc_frame_result& LastFrame() const { return m_frame; }
+
 private:
     mage_reloc_settings m_settings;
     int m_device;
     mage_reloc_pnp_result m_last{};
+    std::vector<mage_reloc_guided_result> m_guided;
+    std::vector<mage_reloc_pnp_result> m_pnp;
+    mage_reloc_frame_result m_frame{};
 };
 
 struct BundlerParameters {

@@ -1187,6 +1187,200 @@ mage_status mage_debug_reloc_pnp_loop(const int32_t* solved, const uint32_t* inl
                                       double confidence, int32_t sequential, int32_t* out);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Relocalisation — the rest of TryEstimatePoseFromCandidates behind PNPRansac                  */
+/* (Tracking/PoseEstimator.cpp:346-436): the first BundleAdjustPose, the guided search, the     */
+/* second BundleAdjustPose, the gates around them and the choice of the candidate              */
+/* ------------------------------------------------------------------------------------------ */
+
+/* A problem's verdict. */
+#define MAGE_RG_OK 0
+#define MAGE_RG_SKIPPED 1            /* the PnP stage did not end MAGE_RP_OK, the frame has fewer keypoints than
+                                        MinBruteForceCorrespondences (:233), the slot is past the frame's candidate
+                                        count, or a status bit below stopped the problem */
+#define MAGE_RG_FEW_RADIUS_MATCHES 2 /* matchCount < MinRadiusMatchCorrespondences (:391) */
+#define MAGE_RG_FEW_MAP_POINTS 3     /* fewer than MinMapPoints left by RemoveMapPointsThatAreBehind (:406) */
+#define MAGE_RG_FEW_BA_INLIERS 4     /* (n - outliers) / (float)n < BundleAdjustInliersPctRequired (:422) */
+
+/* Bits of a problem's status word. */
+#define MAGE_RG_STATUS_OVER_LIMIT 1u /* over 4096 keypoints on a side, or a count over its pitch */
+#define MAGE_RG_STATUS_OVER_CAP 2u   /* more guided queries than `cap` (n_queries reports cap; the rest is dropped) */
+#define MAGE_RG_STATUS_BAD_ORDER 4u  /* an order entry names no keypoint of the candidate, or one with no map point */
+
+/* What the stage decides for one problem; written whole for every problem, zero (the poses the
+ * identity) where a step was not reached.  Poses as mage_ba_pose_batch takes them. */
+typedef struct mage_reloc_guided_result {
+    uint32_t verdict;          /* MAGE_RG_* */
+    uint32_t status;           /* MAGE_RG_STATUS_* bits; with OVER_LIMIT or BAD_ORDER the problem has no other output */
+    uint32_t n_assoc;          /* the candidate's associations that were projected */
+    uint32_t n_queries;        /* those with Distance >= 0 (:363): the RadiusMatch queries (at most cap) */
+    uint32_t n_radius_matches; /* matchCount (:376) */
+    uint32_t n_in_front;       /* the associations RemoveMapPointsThatAreBehind leaves (:405): n of the second BA */
+    uint32_t n_outliers;       /* the second bundle adjustment's outliers */
+    float pos3_first[3], r9_first[9]; /* the pose after the first BundleAdjustPose (:346-347) */
+    float pos3[3], r9[9];             /* the pose after the second (:419); the frame's pose when MAGE_RG_OK */
+} mage_reloc_guided_result;
+
+/* The routine's outcome for one lost frame. */
+typedef struct mage_reloc_frame_result {
+    int32_t index;    /* indexOfSuccess: the lowest candidate whose pass succeeds, or -1 */
+    uint32_t n_assoc; /* the associations the frame takes (that candidate's n_in_front), 0 without success */
+    float pos3[3], r9[9]; /* the frame's pose (the identity without success) */
+} mage_reloc_frame_result;
+
+/* The stage's buffers.  struct_size must be sizeof(mage_reloc_guided_args).  The problems are laid
+ * out frames x candidates_per_frame, problem = frame * candidates_per_frame + candidate; d_n_candidates
+ * (one count per frame; NULL: candidates_per_frame each) tells how many of a frame's slots hold a
+ * candidate.  Every per-problem array is indexed by problem, as the PnP stage's are: the lost
+ * frame's keypoints, descriptors and intrinsics are repeated for each of its candidates.
+ * Inputs: d_intr4 {cx, cy, fx, fy} of the lost frame (the projection, :358); d_ba_intr4 those of
+ * the candidate for both bundle adjustments (:177), NULL = d_intr4; d_map_xyzi / d_kf_kp / d_kf_desc
+ * kf_pitch entries of the candidate (map point {x, y, z, information}, keypoint, 32-byte
+ * descriptor), d_n_kf valid; d_order NULL, or kf_pitch candidate keypoint indices per problem in
+ * IterateAssociations' order, d_n_order of them valid (NULL order: ascending keypoint index over
+ * those with information > 0); d_kp / d_desc kp_pitch entries of the lost frame, d_n_kp valid;
+ * then the PnP stage's outputs as it left them.
+ * Outputs per problem, `cap` entries each unless noted: the RadiusMatch queries (d_query_kp,
+ * d_query_pos 2 floats, d_query_desc 32 bytes, d_query_ref the candidate keypoint) and their count
+ * d_n_queries; d_radius_matches / d_n_radius as mage_radius_match_batch_device leaves them;
+ * d_assoc {candidate keypoint, frame keypoint} per association (n_in_front written);
+ * d_ba_obs_start (problems + 1) and d_ba_points3 / d_ba_uv / d_ba_info / d_ba_outlier the second
+ * bundle adjustment's observations, compacted over the problems (problems x cap at most);
+ * d_result; d_frame_result (one per frame); d_qt7_first / d_qt7 as mage_ba_pose_batch_device's
+ * d_qt7_out, for every problem, those without observations included.  d_scratch: mage_reloc_guided_scratch_bytes(...) bytes,
+ * 256-byte aligned. */
+typedef struct mage_reloc_guided_args {
+    uint32_t struct_size;
+    uint32_t frames, candidates_per_frame, cap;
+    uint32_t pnp_cap; /* the `cap` the PnP stage ran with: its observations per problem at most */
+    int32_t pose_max_hamming_distance;   /* PoseEstimationSettings.OrbMatcherSettings.MaxHammingDistance 30 */
+    int32_t pose_min_hamming_difference; /* ... MinHammingDifference 1 */
+    int64_t kf_pitch, kp_pitch;
+    const uint32_t* d_n_candidates;
+    const float *d_intr4, *d_ba_intr4, *d_map_xyzi;
+    const mage_keypoint* d_kf_kp;
+    const uint8_t* d_kf_desc;
+    const uint32_t* d_n_kf;
+    const int32_t* d_order;
+    const uint32_t* d_n_order;
+    const mage_keypoint* d_kp;
+    const uint8_t* d_desc;
+    const uint32_t* d_n_kp;
+    const mage_reloc_pnp_result* d_pnp_result;
+    const uint32_t* d_obs_start;
+    const float *d_points3, *d_uv, *d_info, *d_pos3, *d_r9;
+    mage_keypoint* d_query_kp;
+    float* d_query_pos;
+    uint8_t* d_query_desc;
+    int32_t* d_query_ref;
+    uint32_t* d_n_queries;
+    mage_dmatch* d_radius_matches;
+    uint32_t* d_n_radius;
+    int32_t* d_assoc;
+    uint32_t* d_ba_obs_start;
+    float *d_ba_points3, *d_ba_uv, *d_ba_info;
+    uint8_t* d_ba_outlier;
+    mage_reloc_guided_result* d_result;
+    mage_reloc_frame_result* d_frame_result;
+    double *d_qt7_first, *d_qt7; /* NULL, or 7 doubles per problem: the two bundle adjustments' fp64 poses */
+    void* d_scratch;
+} mage_reloc_guided_args;
+
+/* Bytes of the stage's scratch for `problems` problems of `cap` entries behind a PnP stage of
+ * `pnp_cap` observations per problem. */
+uint64_t mage_reloc_guided_scratch_bytes(uint32_t problems, uint32_t cap, uint32_t pnp_cap);
+
+/* The stage behind mage_reloc_pnp_batch_device on `stream`, no host step:
+ *   a. mage_ba_pose_batch_device(bundle_adjust_iterations steps, Huber 1.8,
+ *      max_bundle_adjust_reprojection_error unsquared as RunBundleAdjustment passes it) on the PnP
+ *      stage's arrays: the first BundleAdjustPose (:346);
+ *   b. the query kernel: limits, order and frame checks, ProjectUndistorted of the candidate's
+ *      associations through the refined pose in float, Distance >= 0 kept in order (:351-371);
+ *   c. mage_radius_match_batch_device at search_radius with the pose estimator's matcher settings;
+ *   d. the gate kernel and the pack kernel: MinRadiusMatchCorrespondences (:391), the matches in
+ *      query order as associations, RemoveMapPointsThatAreBehind (:405), MinMapPoints (:406); then
+ *      d_ba_obs_start as the prefix of the counts and the second bundle adjustment's inputs;
+ *   e. mage_ba_pose_batch_device again, with outliers (:419);
+ *   f. the decide kernel, one workgroup per frame: the outlier counts, the
+ *      BundleAdjustInliersPctRequired gate (:422), the result records and the frame's record.
+ * The frame's record names the lowest candidate index whose pass succeeds: every round of the
+ * reference's round-robin repeats the same RANSAC and everything behind it is a function of its
+ * result, so for round_robin_iterations >= 1 that is indexOfSuccess; with 0 rounds it is -1.
+ * Candidates behind the winner are computed and reported all the same, where the reference would
+ * not have looked at them.  An OVER_LIMIT or BAD_ORDER problem gets its status bit and the identity
+ * poses and nothing else of it is written; nothing is written past a problem's counts; the other
+ * problems are unaffected.  Order entries are not checked for repeats.  The candidate's own gate
+ * (:269, fewer associated keypoints than MinBruteForceCorrespondences) is not repeated: IndexedMatch
+ * gives at most one match per associated keypoint, so the PnP stage's gate (:291) has stopped it. */
+mage_status mage_reloc_guided_batch_device(const mage_reloc_settings* settings, const mage_reloc_guided_args* args,
+                                           mage_stream stream);
+
+/* One lost frame with n_candidates candidates, host buffers, synchronous, on `device`: the PnP
+ * stage, then the stage above.  Candidate arrays are pitched by kf_pitch (map_xyzi, kf_kp, kf_desc,
+ * order) and match_cap (matches); order / n_order / ba_intr4 may be NULL; ba_intr4 is 4 floats per
+ * candidate.  Outputs: results and pnp_results (NULL allowed) n_candidates records, frame one
+ * record, assoc n_candidates x cap x 2 (n_in_front pairs written per candidate, for every
+ * candidate that reached the second bundle adjustment). */
+mage_status mage_reloc_guided(const mage_reloc_settings* settings, int32_t pose_max_hamming_distance,
+                              int32_t pose_min_hamming_difference, uint32_t n_candidates, const float* intr4,
+                              const float* ba_intr4, const float* map_xyzi, const mage_keypoint* kf_kp,
+                              const uint8_t* kf_desc, uint32_t kf_pitch, const uint32_t* n_kf, const int32_t* order,
+                              const uint32_t* n_order, const mage_keypoint* kp, const uint8_t* desc, uint32_t n_kp,
+                              const mage_dmatch* matches, uint32_t match_cap, const uint32_t* n_matches, uint32_t cap,
+                              mage_reloc_guided_result* results, mage_reloc_pnp_result* pnp_results,
+                              mage_reloc_frame_result* frame, int32_t* assoc, int device);
+
+/* What mage_reloc_candidates_batch_device needs on top of mage_reloc_guided_args: per problem the
+ * BoW leaves of the candidate's (kf_pitch) and of the lost frame's (kp_pitch) descriptors, the
+ * candidate's associated-keypoint mask (kf_pitch bytes, GetAssociatedKeypointMask), and the buffers
+ * IndexedMatch and the PnP stage write: d_matches problems x match_cap with d_n_matches, d_match_status
+ * one word (mage_indexed_match_batch_device's; zeroed by the call), then the PnP stage's outputs and
+ * scratch as mage_reloc_pnp_batch_device takes them with cap = match_cap and no trace.
+ * struct_size must be sizeof(mage_reloc_candidates_args). */
+typedef struct mage_reloc_candidates_args {
+    uint32_t struct_size;
+    uint32_t match_cap;
+    const uint32_t *d_leaf_kf, *d_leaf;
+    const uint8_t* d_mask_kf;
+    mage_dmatch* d_matches;
+    uint32_t *d_n_matches, *d_match_status;
+    mage_reloc_pnp_result* d_pnp_result;
+    uint32_t *d_inlier_idx, *d_obs_start;
+    float *d_points3, *d_uv, *d_info, *d_pos3, *d_r9;
+    void* d_pnp_scratch;
+} mage_reloc_candidates_args;
+
+/* The routine from IndexedMatch on (:279-436) on `stream`, no host step:
+ * mage_indexed_match_batch_device (A = the candidate under its associated-keypoint mask, B = the lost
+ * frame, the relocaliser's OrbMatcherSettings), mage_reloc_pnp_batch_device on its matches, then
+ * mage_reloc_guided_batch_device.  `guided` is filled as for that call except its PnP-stage fields
+ * (d_pnp_result, d_obs_start, d_points3, d_uv, d_info, d_pos3, d_r9, pnp_cap), which are taken from
+ * `cand`.  A problem with more matches than match_cap is the PnP stage's OVER_LIMIT and so SKIPPED. */
+mage_status mage_reloc_candidates_batch_device(const mage_reloc_settings* settings, const mage_reloc_candidates_args* cand,
+                                               const mage_reloc_guided_args* guided, mage_stream stream);
+
+/* The twin in plain C++ for one problem, no GPU, byte-identical to the kernels phase by phase.  The
+ * library has no host pose bundle adjustment and no host RadiusMatch, so their outcomes are inputs.
+ *   1. from the first refined pose (pos3_first, r9_first) and pnp_ok (the PnP stage ended
+ *      MAGE_RP_OK without a stopping status bit): the checks and the query set (query_* / n_queries);
+ *   2. radius_matches != NULL: the gates, the association records and the second bundle
+ *      adjustment's inputs (n_in_front entries);
+ *   3. outlier != NULL (n_in_front flags) with pos3_second / r9_second: the final record.
+ * A NULL stops after the phase before it; *result is what the kernels hold at that point. */
+mage_status mage_reloc_guided_host(const mage_reloc_settings* settings, int32_t pnp_ok, const float* intr4,
+                                   const float* map_xyzi, const mage_keypoint* kf_kp, const uint8_t* kf_desc,
+                                   uint32_t n_kf, const int32_t* order, uint32_t n_order, const mage_keypoint* kp,
+                                   uint32_t n_kp, const float* pos3_first, const float* r9_first, uint32_t cap,
+                                   mage_reloc_guided_result* result, mage_keypoint* query_kp, float* query_pos,
+                                   uint8_t* query_desc, int32_t* query_ref, const mage_dmatch* radius_matches,
+                                   uint32_t n_radius_matches, int32_t* assoc, float* ba_points3, float* ba_uv,
+                                   float* ba_info, const uint8_t* outlier, const float* pos3_second,
+                                   const float* r9_second);
+
+/* The frame's record from its candidates' records (the decide kernel's last step). */
+mage_status mage_reloc_guided_choose_host(const mage_reloc_settings* settings, const mage_reloc_guided_result* results,
+                                          uint32_t n_candidates, mage_reloc_frame_result* frame);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Local bundle adjustment — replaces BundlerLib (Dependencies/BundlerLib/Include/BundlerLib.h) */
 /* ------------------------------------------------------------------------------------------ */
 

@@ -48,6 +48,8 @@ EXPORTS = [
     "mage_mono_init_third_frame_host",
     "mage_reloc_pnp_trace_bytes", "mage_reloc_pnp_scratch_bytes", "mage_reloc_pnp_batch_device", "mage_reloc_pnp",
     "mage_reloc_pnp_host", "mage_debug_reloc_pnp_update", "mage_debug_reloc_pnp_loop",
+    "mage_reloc_guided_scratch_bytes", "mage_reloc_guided_batch_device", "mage_reloc_guided", "mage_reloc_guided_host",
+    "mage_reloc_guided_choose_host", "mage_reloc_candidates_batch_device",
 ]
 
 
@@ -249,6 +251,50 @@ RP_RESULT_DTYPE = np.dtype([("verdict", "<u4"), ("status", "<u4"), ("n_matches",
                             ("win_indices", "<i4", 5), ("iterations", "<u4"), ("iterations_run", "<u4"),
                             ("pos3", "<f4", 3), ("r9", "<f4", 9)])
 
+# mage_reloc_guided_result (124 B)
+RG_RESULT_DTYPE = np.dtype([("verdict", "<u4"), ("status", "<u4"), ("n_assoc", "<u4"), ("n_queries", "<u4"),
+                            ("n_radius_matches", "<u4"), ("n_in_front", "<u4"), ("n_outliers", "<u4"),
+                            ("pos3_first", "<f4", 3), ("r9_first", "<f4", 9), ("pos3", "<f4", 3), ("r9", "<f4", 9)])
+
+# mage_reloc_frame_result (56 B)
+RG_FRAME_DTYPE = np.dtype([("index", "<i4"), ("n_assoc", "<u4"), ("pos3", "<f4", 3), ("r9", "<f4", 9)])
+
+
+class RelocGuidedArgsC(C.Structure):
+    """mage_reloc_guided_args (include/mage_hot.h); struct_size is filled in by make(), pointers are
+    given as anything ptr() takes."""
+    _POINTERS = ("d_n_candidates", "d_intr4", "d_ba_intr4", "d_map_xyzi", "d_kf_kp", "d_kf_desc", "d_n_kf", "d_order",
+                 "d_n_order", "d_kp", "d_desc", "d_n_kp", "d_pnp_result", "d_obs_start", "d_points3", "d_uv", "d_info",
+                 "d_pos3", "d_r9", "d_query_kp", "d_query_pos", "d_query_desc", "d_query_ref", "d_n_queries",
+                 "d_radius_matches", "d_n_radius", "d_assoc", "d_ba_obs_start", "d_ba_points3", "d_ba_uv", "d_ba_info",
+                 "d_ba_outlier", "d_result", "d_frame_result", "d_qt7_first", "d_qt7", "d_scratch")
+    _fields_ = ([("struct_size", C.c_uint32), ("frames", C.c_uint32), ("candidates_per_frame", C.c_uint32),
+                 ("cap", C.c_uint32), ("pnp_cap", C.c_uint32), ("pose_max_hamming_distance", C.c_int32),
+                 ("pose_min_hamming_difference", C.c_int32), ("kf_pitch", C.c_int64), ("kp_pitch", C.c_int64)] +
+                [(name, C.c_void_p) for name in _POINTERS])
+
+    @classmethod
+    def make(cls, **kw):
+        for name in cls._POINTERS:
+            if name in kw:
+                kw[name] = ptr(kw[name])
+        return cls(struct_size=C.sizeof(cls), **kw)
+
+
+class RelocCandidatesArgsC(C.Structure):
+    """mage_reloc_candidates_args (include/mage_hot.h); as RelocGuidedArgsC."""
+    _POINTERS = ("d_leaf_kf", "d_leaf", "d_mask_kf", "d_matches", "d_n_matches", "d_match_status", "d_pnp_result",
+                 "d_inlier_idx", "d_obs_start", "d_points3", "d_uv", "d_info", "d_pos3", "d_r9", "d_pnp_scratch")
+    _fields_ = [("struct_size", C.c_uint32), ("match_cap", C.c_uint32)] + [(name, C.c_void_p) for name in _POINTERS]
+
+    @classmethod
+    def make(cls, **kw):
+        for name in cls._POINTERS:
+            if name in kw:
+                kw[name] = ptr(kw[name])
+        return cls(struct_size=C.sizeof(cls), **kw)
+
+
 # mage_new_point_assoc (16 B)
 NA_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("octave", "<i4"), ("keypoint", "<i4")])
 
@@ -408,6 +454,14 @@ def _declare(L: C.CDLL) -> None:
     sig("mage_reloc_pnp_host", st, vp, vp, vp, u32, vp, u32, vp, u32, vp, vp, u32, vp, vp, vp, vp)
     sig("mage_debug_reloc_pnp_update", st, f64, u32, u32, vp)
     sig("mage_debug_reloc_pnp_loop", st, vp, vp, u32, u32, f64, i32, vp)
+    sig("mage_reloc_guided_scratch_bytes", u64, u32, u32, u32)
+    sig("mage_reloc_guided_batch_device", st, vp, vp, vp)
+    sig("mage_reloc_guided", st, vp, i32, i32, u32, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, vp, u32, vp, u32,
+        vp, vp, vp, vp, C.c_int)
+    sig("mage_reloc_guided_host", st, vp, i32, vp, vp, vp, vp, u32, vp, u32, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp,
+        vp, u32, vp, vp, vp, vp, vp, vp, vp)
+    sig("mage_reloc_guided_choose_host", st, vp, vp, u32, vp)
+    sig("mage_reloc_candidates_batch_device", st, vp, vp, vp, vp)
     sig("mage_overlap_crop_source_in_target", st, vp, vp, vp, f32, vp)
     sig("mage_stereo_map_init", st, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp, C.c_int)
     sig("mage_debug_stereo_init_host", st, vp, vp, vp, vp, vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp)
