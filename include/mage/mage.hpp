@@ -1299,5 +1299,139 @@ private:
     std::vector<uint32_t> m_cam, m_pt;
 };
 
+// BoundingDepthSettings (MageSettings.h:216-223).
+struct BoundingDepthSettings {
+    float RegionOfInterestMinX{0.1f}, RegionOfInterestMinY{0.1f}, RegionOfInterestMaxX{0.9f}, RegionOfInterestMaxY{0.9f};
+    float NearDepthSoftness{0.f}, FarDepthSoftness{0.f};
+
+    mage_bounding_depth_settings ToC() const
+    {
+        mage_bounding_depth_settings s{};
+        s.struct_size = (uint32_t)sizeof(s);
+        s.region_of_interest_min_x = RegionOfInterestMinX;
+        s.region_of_interest_min_y = RegionOfInterestMinY;
+        s.region_of_interest_max_x = RegionOfInterestMaxX;
+        s.region_of_interest_max_y = RegionOfInterestMaxY;
+        s.near_depth_softness = NearDepthSoftness;
+        s.far_depth_softness = FarDepthSoftness;
+        return s;
+    }
+};
+
+using ProjectedPoint = mage_projected_point;  // Data/Data.h:112-124
+
+// InternalDepth (Data/Data.h): the two plane depths and the sparse depth map it owns.
+struct InternalDepth {
+    static constexpr float INVALID_DEPTH = MAGE_INVALID_DEPTH;
+    float NearPlaneDepth{INVALID_DEPTH}, FarPlaneDepth{INVALID_DEPTH};
+    std::vector<ProjectedPoint> SparseDepth;
+    mage_depth_result Result{};  // the counts and the status bits
+};
+
+// CalculateBoundingPlaneDepthsForKeyframe (Tracking/BoundingPlaneDepths.cpp:16-87).  The keyframe is
+// given as what the routine reads of it: the view matrix in the bundler form, the undistorted
+// calibration {cx, cy, fx, fy}, the image size, the keypoints, and per associated map point its
+// position with the id's bits {x, y, z, id} and the index of its keypoint (GetAssociatedKeyPoint).
+// device < 0 runs the CPU backend.  Throws Error (MAGE_EUNSUPPORTED) for more than
+// MAGE_BD_MAX_POINTS map points and std::out_of_range for a keypoint index outside the keypoints.
+inline InternalDepth CalculateBoundingPlaneDepthsForKeyframe(const ViewPose& pose, const std::array<float, 4>& calibration,
+                                                             uint32_t width, uint32_t height,
+                                                             const std::vector<KeyPoint>& keypoints,
+                                                             const std::vector<std::array<float, 4>>& mapPoints,
+                                                             const std::vector<int32_t>& associatedKeypoints,
+                                                             const BoundingDepthSettings& settings, int device = 0)
+{
+    if (mapPoints.size() != associatedKeypoints.size()) throw std::invalid_argument("one keypoint index per map point");
+    const mage_bounding_depth_settings s = settings.ToC();
+    const uint32_t n = (uint32_t)mapPoints.size();
+    InternalDepth d;
+    d.SparseDepth.resize(n);
+    const float* map = n ? mapPoints[0].data() : nullptr;
+    if (device < 0)
+        check(mage_bounding_plane_depths_host(&s, pose.Position.data(), pose.Rotation.data(), calibration.data(), width,
+                                              height, keypoints.data(), (uint32_t)keypoints.size(), map,
+                                              associatedKeypoints.data(), n, n, &d.Result, d.SparseDepth.data()));
+    else
+        check(mage_bounding_plane_depths(&s, pose.Position.data(), pose.Rotation.data(), calibration.data(), width, height,
+                                         keypoints.data(), (uint32_t)keypoints.size(), map, associatedKeypoints.data(), n,
+                                         n, &d.Result, d.SparseDepth.data(), device));
+    if (d.Result.status & MAGE_BD_STATUS_OVER_LIMIT) throw Error(MAGE_EUNSUPPORTED, "more than 8192 map points in a frame");
+    if (d.Result.status & MAGE_BD_STATUS_BAD_INDEX) throw std::out_of_range("a map point names no keypoint");
+    d.NearPlaneDepth = d.Result.near_plane;
+    d.FarPlaneDepth = d.Result.far_plane;
+    return d;
+}
+
+// VolumeOfInterestSettings (MageSettings.h:290-307).
+struct VolumeOfInterestSettings {
+    float Threshold{0.5f};
+    int Iterations{3}, VoxelCountFloor{16000};
+    float AwayProminence{1.2f}, TowardProminence{0.1f}, SideProminence{1.f};
+    float KernelAngleXRads{1.04719755f}, KernelAngleYRads{0.69813170f};  // deg2rad(60), deg2rad(40)
+    float KernelPitchRads{0.f}, KernelRollRads{0.f}, KernelYawRads{0.08726646f};  // deg2rad(5)
+    float KernelDepthModifier{1.f};
+
+    mage_voi_settings ToC() const
+    {
+        mage_voi_settings s{};
+        s.struct_size = (uint32_t)sizeof(s);
+        s.threshold = Threshold;
+        s.iterations = Iterations;
+        s.voxel_count_floor = VoxelCountFloor;
+        s.away_prominence = AwayProminence;
+        s.toward_prominence = TowardProminence;
+        s.side_prominence = SideProminence;
+        s.kernel_angle_x_rads = KernelAngleXRads;
+        s.kernel_angle_y_rads = KernelAngleYRads;
+        s.kernel_pitch_rads = KernelPitchRads;
+        s.kernel_roll_rads = KernelRollRads;
+        s.kernel_yaw_rads = KernelYawRads;
+        s.kernel_depth_modifier = KernelDepthModifier;
+        return s;
+    }
+};
+
+// AxisAlignedVolume (Data/Data.h).
+struct AxisAlignedVolume {
+    std::array<float, 3> Min{}, Max{};
+};
+
+// What VOIKeyframe's constructor reads (VolumeOfInterest.cpp:45-61): the world-from-camera matrix
+// (3 x 4, row-major: ToPose(WorldPosition)'s inverse view matrix) and the frame's plane depths.
+struct VOIKeyframe {
+    std::array<float, 12> WorldFromCamera;
+    float NearDepth, FarDepth;
+};
+
+// CalculateVolumeOfInterest (VolumeOfInterest.cpp:88-259): false without keyframes (`voi` untouched),
+// true otherwise, as the reference returns; `result`, when given, receives the status
+// (MAGE_VOI_DEGENERATE / MAGE_VOI_EMPTY: `voi` holds what the last level that passed left) and
+// `trace` the per-level records.  device < 0 runs the CPU backend.
+inline bool CalculateVolumeOfInterest(const std::vector<VOIKeyframe>& keyframes, const VolumeOfInterestSettings& voiSettings,
+                                      AxisAlignedVolume& voi, mage_voi_result* result = nullptr,
+                                      std::vector<mage_voi_level>* trace = nullptr, int device = 0)
+{
+    const mage_voi_settings s = voiSettings.ToC();
+    const uint32_t n = (uint32_t)keyframes.size();
+    std::vector<float> m(12 * (size_t)n), nf(2 * (size_t)n);
+    for (uint32_t k = 0; k < n; k++) {
+        std::copy(keyframes[k].WorldFromCamera.begin(), keyframes[k].WorldFromCamera.end(), &m[12 * (size_t)k]);
+        nf[2 * (size_t)k] = keyframes[k].NearDepth;
+        nf[2 * (size_t)k + 1] = keyframes[k].FarDepth;
+    }
+    mage_voi_result r{};
+    std::vector<mage_voi_level> levels((size_t)std::max(voiSettings.Iterations, 0));
+    if (device < 0)
+        check(mage_volume_of_interest_host(&s, m.data(), nf.data(), nullptr, 0, nullptr, n, &r, levels.data()));
+    else
+        check(mage_volume_of_interest(&s, m.data(), nf.data(), nullptr, 0, nullptr, n, &r, levels.data(), device));
+    if (result) *result = r;
+    if (r.status == MAGE_VOI_NO_KEYFRAMES) return false;
+    if (trace) *trace = levels;
+    std::copy(r.min, r.min + 3, voi.Min.begin());
+    std::copy(r.max, r.max + 3, voi.Max.begin());
+    return true;
+}
+
 }  // namespace hot
 }  // namespace mage

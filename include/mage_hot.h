@@ -1381,6 +1381,203 @@ mage_status mage_reloc_guided_choose_host(const mage_reloc_settings* settings, c
                                           uint32_t n_candidates, mage_reloc_frame_result* frame);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Scene extent — CalculateBoundingPlaneDepthsForKeyframe (Tracking/BoundingPlaneDepths.cpp:    */
+/* 16-87): a tracked frame's near and far plane depths and its sparse depth map                */
+/* ------------------------------------------------------------------------------------------ */
+
+/* BoundingDepthSettings (MageSettings.h:216-223) in the reference's order.  struct_size must be
+ * sizeof(mage_bounding_depth_settings).  Both softness values must lie in [0, 1): the reference
+ * would index past the end of its depth list with anything else (MAGE_EINVAL here). */
+typedef struct mage_bounding_depth_settings {
+    uint32_t struct_size;
+    float region_of_interest_min_x; /* RegionOfInterestMinX 0.1, a share of the image width */
+    float region_of_interest_min_y; /* RegionOfInterestMinY 0.1 */
+    float region_of_interest_max_x; /* RegionOfInterestMaxX 0.9 */
+    float region_of_interest_max_y; /* RegionOfInterestMaxY 0.9 */
+    float near_depth_softness;      /* NearDepthSoftness 0: the share of the valid depths ruled out at the near end */
+    float far_depth_softness;       /* FarDepthSoftness 0 */
+} mage_bounding_depth_settings;
+
+#define MAGE_INVALID_DEPTH (-1.0f) /* Depth::INVALID_DEPTH (Data/Data.h:390) */
+#define MAGE_BD_MAX_POINTS 8192u   /* map points per frame: the depth list is 32 KB of LDS */
+
+/* Bits of a frame's status word. */
+#define MAGE_BD_STATUS_BAD_INDEX 1u   /* a keypoint index outside the frame's count: the point contributes no valid
+                                         depth, its sparse record is still written */
+#define MAGE_BD_STATUS_NONPOSITIVE 2u /* a valid depth that is not > 0 (the reference asserts, :50); values reported all the same */
+#define MAGE_BD_STATUS_OVER_LIMIT 4u  /* n_points over `cap`, or `cap` over MAGE_BD_MAX_POINTS: the record is
+                                         {-1, -1, 0, n_points} and nothing else of the frame is written */
+
+/* ProjectedPoint (Data/Data.h:112-124), 16 bytes: a map point through ProjectUndistorted
+ * (Tracking/Reprojection.cpp:26-42; a camera-space depth of exactly 0 divides by 1) and its id. */
+typedef struct mage_projected_point {
+    float x, y, depth;
+    int32_t id;
+} mage_projected_point;
+
+/* InternalDepth without its sparse map, 20 bytes. */
+typedef struct mage_depth_result {
+    float near_plane; /* NearPlaneDepth, MAGE_INVALID_DEPTH when near > far (no valid depth) */
+    float far_plane;  /* FarPlaneDepth */
+    uint32_t n_valid; /* points whose keypoint lies inside the closed region of interest */
+    uint32_t n_points;
+    uint32_t status;  /* MAGE_BD_STATUS_* bits */
+} mage_depth_result;
+
+/* One frame on the calling thread in plain C++, the CPU backend, bit-identical to the kernel.  The
+ * pose is the view matrix in the bundler form (pos3 view-space t, r9 column-major R), intr4 = {cx,
+ * cy, fx, fy} of the undistorted calibration.  The world position c and forward f are column 3 and
+ * column 2 of Utils/cv.h Invert(view) (Data/Pose.cpp:110-118), c formed as -(R^T t) the way the
+ * third-frame stage forms camera centres: cv::Matx's product differs in the sign of a zero only.
+ * Point i is map_xyzi[4 i .. 4 i + 3] = {x, y, z, the id's 32 bits} and is associated with keypoint
+ * kp_index[i] of the frame's n_kp keypoints.  With the region bounds min/max x = share * width and
+ * min/max y = share * height as float products, a point whose keypoint lies inside the closed region
+ * adds depth = (p - c) . f to the valid depths; every point gets sparse[i] in point order.
+ * near_plane is the valid depth of rank (size_t)(near_depth_softness * n_valid) in ascending order,
+ * far_plane the one of rank (size_t)(far_depth_softness * n_valid) in descending order, the product
+ * taken in float, a rank that rounds up to n_valid held at n_valid - 1; depths compare under the
+ * total order of their bit patterns in which -0 < +0, so any exact selection gives the same bits.
+ * Without a valid depth near stays FLT_MAX and far FLT_MIN (the smallest positive normal, the
+ * reference's start value), near > far, and both become MAGE_INVALID_DEPTH; so they do when the two
+ * softness values make the ranks cross.  `cap` is what `sparse` holds. */
+mage_status mage_bounding_plane_depths_host(const mage_bounding_depth_settings* settings, const float* pos3,
+                                            const float* r9, const float* intr4, uint32_t width, uint32_t height,
+                                            const mage_keypoint* kp, uint32_t n_kp, const float* map_xyzi,
+                                            const int32_t* kp_index, uint32_t n_points, uint32_t cap,
+                                            mage_depth_result* result, mage_projected_point* sparse);
+
+/* The same through the kernel: host buffers, synchronous, on `device`. */
+mage_status mage_bounding_plane_depths(const mage_bounding_depth_settings* settings, const float* pos3, const float* r9,
+                                       const float* intr4, uint32_t width, uint32_t height, const mage_keypoint* kp,
+                                       uint32_t n_kp, const float* map_xyzi, const int32_t* kp_index, uint32_t n_points,
+                                       uint32_t cap, mage_depth_result* result, mage_projected_point* sparse, int device);
+
+/* `frames` frames in one launch on `stream`, one workgroup per frame: the projection and the region
+ * test by the threads, the two order statistics by a radix selection over the depth list in LDS.
+ * Per frame f: d_pos3 3, d_r9 9, d_intr4 4 floats; d_size {width, height}; d_kp kp_pitch keypoints,
+ * d_n_kp[f] of them valid (a count over kp_pitch is read as kp_pitch); d_map_xyzi point_pitch x 4
+ * floats and d_kp_index point_pitch words, d_n_points[f] of them valid; d_result one record;
+ * d_sparse point_pitch records, d_n_points[f] written.  cap <= point_pitch.  Nothing is written past
+ * a frame's counts; an OVER_LIMIT frame gets its record only; the other frames are unaffected.
+ * d_result can be read by index by a later stage on the same stream. */
+mage_status mage_bounding_plane_depths_batch_device(const mage_bounding_depth_settings* settings, uint32_t frames,
+                                                    const float* d_pos3, const float* d_r9, const float* d_intr4,
+                                                    const uint32_t* d_size, const mage_keypoint* d_kp, int64_t kp_pitch,
+                                                    const uint32_t* d_n_kp, const float* d_map_xyzi,
+                                                    const int32_t* d_kp_index, int64_t point_pitch,
+                                                    const uint32_t* d_n_points, uint32_t cap, mage_depth_result* d_result,
+                                                    mage_projected_point* d_sparse, mage_stream stream);
+
+/* ------------------------------------------------------------------------------------------ */
+/* Scene extent — CalculateVolumeOfInterest (VolumeOfInterest/VolumeOfInterest.cpp:45-259)     */
+/* behind MAGESlam::TryGetVolumeOfInterest (MageSlam.h:119, 178; Map/PoseHistory.cpp:58-75)    */
+/* ------------------------------------------------------------------------------------------ */
+
+/* VolumeOfInterestSettings (MageSettings.h:290-307) in the reference's order, then the constants
+ * mage_voi_settings_prepare derives from them.  struct_size must be sizeof(mage_voi_settings);
+ * iterations must be in 0..MAGE_VOI_MAX_ITERATIONS.  Every entry below derives the constants again
+ * on a copy, so a caller need not prepare. */
+typedef struct mage_voi_settings {
+    uint32_t struct_size;
+    float threshold;             /* Threshold 0.5 */
+    int32_t iterations;          /* Iterations 3 */
+    int32_t voxel_count_floor;   /* VoxelCountFloor 16000 */
+    float away_prominence;       /* AwayProminence 1.2 */
+    float toward_prominence;     /* TowardProminence 0.1 */
+    float side_prominence;       /* SideProminence 1 */
+    float kernel_angle_x_rads;   /* KernelAngleXRads deg2rad(60) */
+    float kernel_angle_y_rads;   /* KernelAngleYRads deg2rad(40) */
+    float kernel_pitch_rads;     /* KernelPitchRads 0 */
+    float kernel_roll_rads;      /* KernelRollRads 0 */
+    float kernel_yaw_rads;       /* KernelYawRads deg2rad(5) */
+    float kernel_depth_modifier; /* KernelDepthModifier 1 */
+    float kernel_rotation[9];    /* derived: ToMat(pitch, roll, yaw) (Utils/cv.h:96-116), row-major */
+    float tan_min_angle;         /* derived: tan(min(angle x, angle y)) (:59) */
+    float tan_half_angle_x;      /* derived: tan(angle x / 2) (:103) */
+    float tan_half_angle_y;      /* derived: tan(angle y / 2) (:104) */
+} mage_voi_settings;
+
+#define MAGE_VOI_MAX_ITERATIONS 30
+#define MAGE_VOI_OK 0
+#define MAGE_VOI_NO_KEYFRAMES 1 /* the reference returns false; the bounds and the trace are untouched */
+#define MAGE_VOI_DEGENERATE 2   /* a level with voxelCount == 0, a diagonal that is <= 0 or not finite, a dims product
+                                   over 2^31 - 1, or a voxel value that is not finite */
+#define MAGE_VOI_EMPTY 3        /* nothing passed a level's threshold */
+
+/* The outcome of one problem.  The level loop stops at the first DEGENERATE or EMPTY level and the
+ * bounds hold what the level before left (the frustum box when the first level stops). */
+typedef struct mage_voi_result {
+    float min[3], max[3];
+    uint32_t status;      /* MAGE_VOI_* */
+    uint32_t levels_done;
+} mage_voi_result;
+
+/* One level's trace record, 60 bytes; a problem has `iterations` of them, zeroed first and filled as
+ * far as the level got (a level that is DEGENERATE by its grid stays zero; one with a voxel value
+ * that is not finite has side, dims, voxel_min and voxel_max). */
+typedef struct mage_voi_level {
+    float side;                   /* voxelSideLength */
+    int32_t dims[3];
+    float voxel_min, voxel_max;   /* minVoxelValue / maxVoxelValue after the level: they run on across the levels */
+    float threshold;
+    float box_min[3], box_max[3]; /* the level's resulting box */
+    uint32_t n_voxels;            /* voxels strictly above the threshold */
+    uint32_t n_centroids;         /* keyframe centroids whose stored score is above it */
+} mage_voi_level;
+
+/* Fills the derived constants with libm on the host (sinf, cosf, tanf, as the reference calls them). */
+mage_status mage_voi_settings_prepare(mage_voi_settings* settings);
+
+/* TeardropScore (:63-86) of n_points points {x, y, z} against n_kf keyframes: scores[p * n_kf + k].
+ * Keyframes as below.  The twin's own function. */
+mage_status mage_voi_teardrop_host(const mage_voi_settings* settings, const float* kf_world, const float* near_far,
+                                   uint32_t n_kf, const float* points, uint32_t n_points, float* scores);
+
+/* One problem (one pose history) on the calling thread in plain C++, bit-identical to the kernels.
+ * kf_world: n_kf world-from-camera matrices, 3 x 4 row-major (the inverse view matrix that
+ * ToPose(WorldPosition) holds).  The keyframes' depths are near_far (n_kf pairs {near, far}), or with
+ * near_far NULL the records depth_records[depth_index[k]] of the depth stage (an index outside
+ * n_depth_records reads as MAGE_INVALID_DEPTH for both).  A depth of -1 is passed through as the
+ * reference passes it.  trace: NULL, or `iterations` records.
+ * Follows VolumeOfInterest.cpp in float with these deviations: acos, exp and the cube root are the
+ * library's own (csrc/scene_math.hpp; acos clamps its argument to [-1, 1]; the reference writes
+ * pow(v, 1.f / 3.f)); minima and maxima are taken under the total order in which -0 < +0; the
+ * status replaces undefined arithmetic.  The maxima start at numeric_limits<float>::min() as the
+ * reference's do, so a maximum never drops below about 1.2e-38. */
+mage_status mage_volume_of_interest_host(const mage_voi_settings* settings, const float* kf_world, const float* near_far,
+                                         const mage_depth_result* depth_records, uint32_t n_depth_records,
+                                         const uint32_t* depth_index, uint32_t n_kf, mage_voi_result* result,
+                                         mage_voi_level* trace);
+
+/* The same through the kernels: host buffers, synchronous, on `device`. */
+mage_status mage_volume_of_interest(const mage_voi_settings* settings, const float* kf_world, const float* near_far,
+                                    const mage_depth_result* depth_records, uint32_t n_depth_records,
+                                    const uint32_t* depth_index, uint32_t n_kf, mage_voi_result* result,
+                                    mage_voi_level* trace, int device);
+
+/* Bytes of mage_volume_of_interest_batch_device's scratch: per problem the keyframes' records and
+ * scores and the levels' accumulators.  Voxel values are not kept: the threshold pass computes them
+ * again. */
+uint64_t mage_volume_of_interest_scratch_bytes(uint32_t problems, uint32_t kf_pitch);
+
+/* `problems` problems as one chain of launches on `stream` with no host step: a setup launch (the
+ * keyframes' records, the frustum box, the keyframe scores), two launches per level (the voxel
+ * values' minimum and maximum; the threshold and the next box) and a closing launch that writes
+ * the last level's outcome.  A fixed number of workgroups per problem walks the voxels with a
+ * grid-stride loop over the count each workgroup derives from the box; the keyframes' records are
+ * staged through LDS in chunks, so n_kf is unbounded.  Per problem: d_kf_world kf_pitch matrices,
+ * d_n_kf valid (a count over kf_pitch is read as kf_pitch); d_near_far kf_pitch pairs, or NULL and
+ * d_depth_index kf_pitch indices into the one array d_depth_records of n_depth_records records (the
+ * depth stage's d_result, on the same stream); d_result one record; d_trace NULL or `iterations`
+ * records; d_scratch 256-byte aligned. */
+mage_status mage_volume_of_interest_batch_device(const mage_voi_settings* settings, uint32_t problems,
+                                                 const float* d_kf_world, int64_t kf_pitch, const uint32_t* d_n_kf,
+                                                 const float* d_near_far, const mage_depth_result* d_depth_records,
+                                                 uint32_t n_depth_records, const uint32_t* d_depth_index,
+                                                 mage_voi_result* d_result, mage_voi_level* d_trace, void* d_scratch,
+                                                 mage_stream stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Local bundle adjustment — replaces BundlerLib (Dependencies/BundlerLib/Include/BundlerLib.h) */
 /* ------------------------------------------------------------------------------------------ */
 

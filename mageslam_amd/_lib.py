@@ -50,6 +50,9 @@ EXPORTS = [
     "mage_reloc_pnp_host", "mage_debug_reloc_pnp_update", "mage_debug_reloc_pnp_loop",
     "mage_reloc_guided_scratch_bytes", "mage_reloc_guided_batch_device", "mage_reloc_guided", "mage_reloc_guided_host",
     "mage_reloc_guided_choose_host", "mage_reloc_candidates_batch_device",
+    "mage_bounding_plane_depths_host", "mage_bounding_plane_depths", "mage_bounding_plane_depths_batch_device",
+    "mage_voi_settings_prepare", "mage_voi_teardrop_host", "mage_volume_of_interest_host", "mage_volume_of_interest",
+    "mage_volume_of_interest_scratch_bytes", "mage_volume_of_interest_batch_device",
 ]
 
 
@@ -208,6 +211,33 @@ class RelocSettingsC(C.Structure):
         return cls(struct_size=C.sizeof(cls), **kw)
 
 
+class BoundingDepthSettingsC(C.Structure):
+    """mage_bounding_depth_settings (include/mage_hot.h); struct_size is filled in by make()."""
+    _fields_ = [("struct_size", C.c_uint32), ("region_of_interest_min_x", C.c_float),
+                ("region_of_interest_min_y", C.c_float), ("region_of_interest_max_x", C.c_float),
+                ("region_of_interest_max_y", C.c_float), ("near_depth_softness", C.c_float),
+                ("far_depth_softness", C.c_float)]
+
+    @classmethod
+    def make(cls, **kw):
+        return cls(struct_size=C.sizeof(cls), **kw)
+
+
+class VoiSettingsC(C.Structure):
+    """mage_voi_settings (include/mage_hot.h); struct_size is filled in by make(), the derived constants by
+    mage_voi_settings_prepare."""
+    _fields_ = [("struct_size", C.c_uint32), ("threshold", C.c_float), ("iterations", C.c_int32),
+                ("voxel_count_floor", C.c_int32), ("away_prominence", C.c_float), ("toward_prominence", C.c_float),
+                ("side_prominence", C.c_float), ("kernel_angle_x_rads", C.c_float), ("kernel_angle_y_rads", C.c_float),
+                ("kernel_pitch_rads", C.c_float), ("kernel_roll_rads", C.c_float), ("kernel_yaw_rads", C.c_float),
+                ("kernel_depth_modifier", C.c_float), ("kernel_rotation", C.c_float * 9), ("tan_min_angle", C.c_float),
+                ("tan_half_angle_x", C.c_float), ("tan_half_angle_y", C.c_float)]
+
+    @classmethod
+    def make(cls, **kw):
+        return cls(struct_size=C.sizeof(cls), **kw)
+
+
 class StereoMapInitResultC(C.Structure):
     """mage_stereo_map_init_result (include/mage_hot.h)."""
     _fields_ = [("code", C.c_int32), ("crop", C.c_int32 * 4), ("n_masked", C.c_uint32), ("n_matches", C.c_uint32),
@@ -258,6 +288,16 @@ RG_RESULT_DTYPE = np.dtype([("verdict", "<u4"), ("status", "<u4"), ("n_assoc", "
 
 # mage_reloc_frame_result (56 B)
 RG_FRAME_DTYPE = np.dtype([("index", "<i4"), ("n_assoc", "<u4"), ("pos3", "<f4", 3), ("r9", "<f4", 9)])
+
+# mage_projected_point (16 B) and mage_depth_result (20 B)
+PP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("depth", "<f4"), ("id", "<i4")])
+BD_RESULT_DTYPE = np.dtype([("near", "<f4"), ("far", "<f4"), ("n_valid", "<u4"), ("n_points", "<u4"), ("status", "<u4")])
+
+# mage_voi_result (32 B) and mage_voi_level (60 B)
+VOI_RESULT_DTYPE = np.dtype([("min", "<f4", 3), ("max", "<f4", 3), ("status", "<u4"), ("levels_done", "<u4")])
+VOI_LEVEL_DTYPE = np.dtype([("side", "<f4"), ("dims", "<i4", 3), ("voxel_min", "<f4"), ("voxel_max", "<f4"),
+                            ("threshold", "<f4"), ("box_min", "<f4", 3), ("box_max", "<f4", 3), ("n_voxels", "<u4"),
+                            ("n_centroids", "<u4")])
 
 
 class RelocGuidedArgsC(C.Structure):
@@ -462,6 +502,16 @@ def _declare(L: C.CDLL) -> None:
         vp, u32, vp, vp, vp, vp, vp, vp, vp)
     sig("mage_reloc_guided_choose_host", st, vp, vp, u32, vp)
     sig("mage_reloc_candidates_batch_device", st, vp, vp, vp, vp)
+    sig("mage_bounding_plane_depths_host", st, vp, vp, vp, vp, u32, u32, vp, u32, vp, vp, u32, u32, vp, vp)
+    sig("mage_bounding_plane_depths", st, vp, vp, vp, vp, u32, u32, vp, u32, vp, vp, u32, u32, vp, vp, C.c_int)
+    sig("mage_bounding_plane_depths_batch_device", st, vp, u32, vp, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, u32, vp, vp,
+        vp)
+    sig("mage_voi_settings_prepare", st, vp)
+    sig("mage_voi_teardrop_host", st, vp, vp, vp, u32, vp, u32, vp)
+    sig("mage_volume_of_interest_host", st, vp, vp, vp, vp, u32, vp, u32, vp, vp)
+    sig("mage_volume_of_interest", st, vp, vp, vp, vp, u32, vp, u32, vp, vp, C.c_int)
+    sig("mage_volume_of_interest_scratch_bytes", u64, u32, u32)
+    sig("mage_volume_of_interest_batch_device", st, vp, u32, vp, i64, vp, vp, vp, u32, vp, vp, vp, vp, vp)
     sig("mage_overlap_crop_source_in_target", st, vp, vp, vp, f32, vp)
     sig("mage_stereo_map_init", st, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp, C.c_int)
     sig("mage_debug_stereo_init_host", st, vp, vp, vp, vp, vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp)
