@@ -128,7 +128,14 @@ class OrbDetector:
         return {"last_gate": lg.value, "next_gate": ng.value, "last_redo": rd.value}
 
     def device_status(self, stream=None) -> None:
+        """Raises what the batched path recorded on the device since the last reset: MAGE_ECAPACITY
+        (a level retained more than 8192 items), MAGE_EUNSUPPORTED (NumCellsX * NumCellsY > 4096).
+        The flags are sticky; DetectAndCompute checks and clears them on every call."""
         check(_lib.load().mage_orb_status(self._h, C.c_void_p(stream) if stream else None))
+
+    def reset_device_status(self, stream=None) -> None:
+        """Clears the sticky device status word (stream-ordered)."""
+        check(_lib.load().mage_orb_reset_status(self._h, C.c_void_p(stream) if stream else None))
 
 
 def fast_score_map(image: np.ndarray, threshold: int = 4, device: int = 0) -> np.ndarray:
