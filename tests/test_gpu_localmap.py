@@ -7,8 +7,9 @@ associated at the start, dense clusters that overflow a point's kept candidates,
 import numpy as np
 import pytest
 
+import local_map_cases as L
 from mageslam_amd import matcher
-from mageslam_amd._lib import KP_DTYPE
+from mageslam_amd._lib import KP_DTYPE, MAGE_EINVAL, MAGE_EUNSUPPORTED, MageError
 
 pytestmark = pytest.mark.gpu
 
@@ -106,3 +107,100 @@ def test_local_map_match_edges(gpu):
     for radius, md in ((0.0, 30), (8.0, -1), (30.0, 256)):
         g, gm, o, om = run_both(qp, qo, qd, kp, desc, np.ones(300, bool), None, radius, md, 1)
         assert np.array_equal(g, o) and np.array_equal(gm, om), (radius, md)
+
+
+# ------------------------- hidden keypoints and masks that decide ---------------------------------
+# The scenes of local_map_cases.py (its docstring says which kernel path each reaches);
+# test_local_map_reference.py asserts on the CPU that hides, masks and order decide results in them.
+
+
+def both_scene(s, hide, radius, md, mdiff):
+    return run_both(s.qp, s.qo, s.qd, s.tk, s.td, s.mask, hide, radius, md, mdiff)
+
+
+def assert_scene(s, hide, radius, md, mdiff, what=None):
+    g, gm, o, om = both_scene(s, hide, radius, md, mdiff)
+    assert np.array_equal(g, o), (what, np.flatnonzero(g != o)[:10])
+    assert np.array_equal(gm, om), (what, np.flatnonzero(gm != om)[:10])
+    return g, gm
+
+
+@pytest.mark.parametrize("name", list(L.G_SCENES))
+def test_local_map_match_hidden_grid(gpu, name):
+    s = L.g_scene(name)
+    g, gm = assert_scene(s, s.hide, s.radius, s.md, s.mdiff)
+    assert np.array_equal(g, s.ref) and np.array_equal(gm, s.ref_mask)  # the independent formulation's too
+    if name == "G2":  # again: the same bytes
+        g2, gm2 = matcher.LocalMapMatch(s.qp, s.qo, s.qd, s.tk, s.td, s.mask, s.radius, s.md, s.mdiff, queryHidden=s.hide)
+        assert g2.tobytes() == g.tobytes() and gm2.tobytes() == gm.tobytes()
+
+
+@pytest.mark.parametrize("blob", L.BLOBS)
+def test_local_map_match_hidden_blob(gpu, blob):
+    """The blob of test_local_map_match_conflicts_and_overflow with hide[q] = q % blob on even q: with
+    9 keypoints a hide leaves a kept list of exactly 8, with 40 only the rescan honours the hide."""
+    s = L.blob_scene(blob)
+    for mdiff in L.BLOB_MDIFFS:
+        g, gm = assert_scene(s, s.hide, L.BLOB_RADIUS, L.BLOB_MD, mdiff, mdiff)
+        assert ((g == s.hide) & (s.hide >= 0)).sum() == 0
+        if blob == 40:
+            g2, gm2 = matcher.LocalMapMatch(s.qp, s.qo, s.qd, s.tk, s.td, s.mask, L.BLOB_RADIUS, L.BLOB_MD, mdiff,
+                                            queryHidden=s.hide)
+            assert g2.tobytes() == g.tobytes() and gm2.tobytes() == gm.tobytes()
+
+
+def test_local_map_match_blocks(gpu):
+    """Three 1024-point blocks of lm_resolve_kernel, the middle one without a single candidate."""
+    s = L.blocks_scene()
+    g, _ = assert_scene(s, None, L.BLOCKS_RADIUS, L.BLOCKS_MD, L.BLOCKS_MDIFF)
+    assert (g[1024:2048] == -1).all() and (g[:1024] >= 0).sum() > (g[2048:] >= 0).sum() >= 1
+
+
+def test_local_map_match_known_answers(gpu):
+    """The hand-written answers of local_map_cases.known_answers, the 4096-keypoint / distance-256
+    packing extremes and the non-finite positions among them."""
+    for c in L.known_answers():
+        g, gm = assert_scene(c, c.hide, c.radius, c.md, c.mdiff, c.name)
+        assert list(g) == c.result and list(gm) == [bool(v) for v in c.final_mask], (c.name, list(g))
+
+
+def test_radius_match_packing_extremes(gpu):
+    """radius.hip packs d << 12 | t and t << 9 | d as ordered_take.hpp does: keypoints 0 and 4095 at
+    distance 256, keypoint 0 masked out."""
+    from oracle import oracle as O
+
+    c = L.packing_extremes(0, True)
+    qk = L.keypoints(c.qp[:, 0], c.qp[:, 1])
+    tmask = np.ones(len(c.tk), bool)
+    tmask[0] = False
+    for mask, train in ((tmask, 4095), (None, 0)):
+        o = O.radius_match(qk, c.qd, c.tk, c.td, c.radius, tmask=None if mask is None else mask.astype(np.uint8),
+                           max_distance=256, min_difference=0)
+        g = matcher.RadiusMatch(qk, c.qd, c.tk, c.td, c.radius, maxHammingDist=256, minHammingDifference=0,
+                                targetKeypointsMask=mask)
+        assert [(int(m["query_idx"]), int(m["train_idx"]), float(m["distance"])) for m in o] == [(0, train, 256.0)]
+        assert g.tobytes() == o.tobytes(), (g, o)
+
+
+@pytest.mark.parametrize("nt", L.MASK_EDGE_NT)
+def test_local_map_match_mask_word_edges(gpu, nt):
+    """One point per keypoint around the 32-bit mask word edges, every second keypoint associated at
+    the start, the last keypoint hidden from the point aimed at it: its bit survives."""
+    c = L.mask_edge_scene(nt)
+    g, gm = assert_scene(c, c.hide, c.radius, c.md, c.mdiff)
+    assert np.array_equal(g, c.result) and np.array_equal(gm, c.final_mask)
+
+
+def test_local_map_match_limits(gpu):
+    rng = np.random.default_rng(3)
+    kp, desc = frame(rng, 4097)
+    qp, qo, qd, _ = queries(rng, kp, desc, 10)
+    with pytest.raises(MageError) as e:
+        matcher.LocalMapMatch(qp, qo, qd, kp, desc, np.ones(4097, bool))
+    assert e.value.status == MAGE_EUNSUPPORTED
+    for md in (257, -2):
+        with pytest.raises(MageError) as e:
+            matcher.LocalMapMatch(qp, qo, qd, kp[:100], desc[:100], np.ones(100, bool), maxHammingDist=md)
+        assert e.value.status == MAGE_EINVAL
+    g, gm, o, om = run_both(qp, qo, qd, kp[:4096], desc[:4096], np.ones(4096, bool))  # the largest frame passes
+    assert np.array_equal(g, o) and np.array_equal(gm, om)
