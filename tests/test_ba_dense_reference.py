@@ -5,6 +5,12 @@ oracle's state to within state_tol = 4 eps (cond2(S) max|dx| + max|state|).  No 
 runs the same comparison in test_gpu_ba_large.py, and the preconditions asserted here (the trial is
 accepted, nothing is removed, the Huber cases really are robustified) are what keeps that test from
 passing for the wrong reason.
+
+The same for ba_cases.TCASES: transform / distance / rotation tethers, points_fixed through the
+general solver and edge lists with their own code paths (a point observed twice by one camera, more
+than 64 observations of a point, points seen by fixed cameras only, points with one observation).
+Cases with distance or rotation tethers are held to state_tol + F d_fd (ba_cases' docstring); the
+mutation checks at the end show what each tolerance still resolves.
 """
 import numpy as np
 import pytest
@@ -104,3 +110,200 @@ def test_state_diff_aligns_quaternion_signs():
     assert B.state_diff((qt, d.xyz), (d.qt, d.xyz)) == 0.0
     qt[2, 5] += 1e-9
     assert abs(B.state_diff((qt, d.xyz), (d.qt, d.xyz)) - 1e-9) < 1e-15
+
+
+# ---- tethers, fixed points, odd edge lists (ba_cases.TCASES) -----------------------------------
+_R = lambda a, b: list(range(a, b))  # noqa: E731
+# case -> (the unknown cameras, the number of point unknowns)
+EXPECTED_UNKNOWNS = {
+    "tr-mixed": (_R(3, 12), 120), "tr-no-shared-points": ([2, 3, 4, 5, 7, 8, 9, 10, 11], 120),
+    "tr-shared-points": (_R(3, 12), 120), "tr-tether-only-camera": (_R(3, 11), 300), "tr-huber": (_R(2, 13), 65),
+    "tr-40-corner": (_R(2, 42), 210), "tr-41": (_R(2, 43), 215), "pf-plain": (_R(3, 12), 0), "pf-tr": (_R(3, 12), 0),
+    "pf-huber": (_R(2, 13), 0), "dup-observation": (_R(3, 12), 120), "long-run-point": (_R(3, 12), 120),
+    "fixed-only-and-single": (_R(3, 12), 120), "dist": (_R(3, 12), 120), "rot": (_R(3, 12), 120),
+    "all-kinds": (_R(3, 12), 120), "all-kinds-41": (_R(2, 43), 215), "all-kinds-pf": (_R(3, 12), 0),
+}
+
+
+def test_every_tether_case_has_its_expectation():
+    assert sorted(EXPECTED_UNKNOWNS) == sorted(B.TCASE_IDS) and sorted(B.FD_F) == sorted(B.FD_CASE_IDS)
+    assert not set(B.TCASE_IDS) & set(B.CASE_IDS)
+
+
+@pytest.mark.parametrize("cid", B.TCASE_IDS)
+def test_oracle_matches_dense_reference_with_tethers(cid):
+    t = B.tcase(cid)
+    g, d = t.g, t.d
+    ob, out = B.oracle_one_trial(g, t.lam, t.huber, t.tethers, t.points_fixed)
+    st = ob.stats()
+    assert st["iterations"] == 1 and st["trials"] == 1 and st["rejected"] == 0
+    assert len(out) == 0
+    cams, npts = EXPECTED_UNKNOWNS[cid]
+    assert d.cams.tolist() == cams and all(g.fixed[c] == 0 for c in cams)
+    assert len(d.pts) == npts and (t.points_fixed or np.array_equal(d.pts, np.arange(len(g.points))))
+    if t.huber < B.NO_HUBER:
+        assert d.robust_frac > 0.5
+    else:
+        assert d.robust_frac == 0.0
+    diff = B.state_diff(ob.state(), t.ref)
+    print(f"{cid}: cond(S) {d.cond_S:.3g} state_tol {t.tight:.3g} d_fd {t.d_fd:.3g} tol {t.tol:.3g} "
+          f"oracle-dense {diff:.3g} ratio to tol {diff / t.tol:.4f}")
+    assert diff <= t.tol
+    assert np.abs(d.x[:6 * len(cams)]).max() > 1e-4
+    if B.tether_count(t.tethers):
+        # the tethers matter: without them the reference is somewhere else entirely
+        nt = t.dense(tethers=None)
+        cams_nt = set(nt.cams.tolist())
+        assert cams_nt <= set(cams)
+        assert B.state_diff((nt.qt, nt.xyz), t.ref) > 100 * t.tol
+    if not B.TCASES[cid].fd:
+        assert t.tol == t.tight and t.d_fd == 0.0  # K = 4 as it stands
+
+
+def test_tether_case_structure():
+    """Each case really has the structure it is named after."""
+    free = lambda g, c: g.fixed[c] == 0  # noqa: E731
+    t = B.tcase("tr-mixed")
+    blocks = B.tether_blocks(t.g, t.tethers)
+    pairs = [(b.c1, b.c2) for b in blocks]
+    assert len(pairs) == len(B.TR_MIXED) - 1 and (0, 2) not in pairs  # the fixed-fixed tether is inactive
+    a, b = pairs[B.TR_MIXED_REVERSED]
+    assert a > b and free(t.g, a) and free(t.g, b)
+    a, b = pairs[B.TR_MIXED_DOUBLED_SECOND]
+    assert (b, a) in pairs and free(t.g, a) and free(t.g, b)
+    assert any(not free(t.g, a) and free(t.g, b) for a, b in pairs)
+    assert any(free(t.g, a) and not free(t.g, b) for a, b in pairs)
+    shared = lambda g, a, b: np.intersect1d(g.pt[g.cam == a], g.pt[g.cam == b]).size  # noqa: E731
+    t = B.tcase("tr-no-shared-points")
+    assert all(shared(t.g, int(a), int(b)) == 0 for a, b in zip(*t.tethers.transform[:2]))
+    t = B.tcase("tr-shared-points")
+    assert all(shared(t.g, int(a), int(b)) > 20 for a, b in zip(*t.tethers.transform[:2]))
+    t = B.tcase("tr-tether-only-camera")
+    extra = len(t.g.pos) - 1
+    assert extra in t.d.cams and not (t.g.cam == extra).any()
+    for cid in ("tr-huber", "pf-huber"):  # a tether above the Huber width: robustifying it would show
+        t = B.tcase(cid)
+        chi2 = [b.om * float(b.e @ b.e) for b in B.tether_blocks(t.g, t.tethers, t.points_fixed)]
+        assert max(chi2) > t.huber ** 2 > min(chi2)
+    t = B.tcase("pf-tr")
+    assert any(free(t.g, b.c1) and free(t.g, b.c2) for b in B.tether_blocks(t.g, t.tethers, True))
+    g = B.tcase("dup-observation").g
+    key = g.cam.astype(np.int64) * len(g.points) + g.pt
+    assert len(key) - len(np.unique(key)) == 20
+    g = B.tcase("long-run-point").g
+    assert np.sort(np.bincount(g.pt))[-2] > 64
+    g = B.tcase("fixed-only-and-single").g
+    assert all(g.fixed[g.cam[g.pt == p]].all() and (g.pt == p).sum() == 3 for p in g.fixed_only)
+    assert all((g.pt == p).sum() == 1 and not g.fixed[g.cam[g.pt == p]].any() for p in g.single)
+    for cid in B.FD_CASE_IDS:
+        t = B.tcase(cid)
+        kinds = (t.tethers.distance, t.tethers.rotation)
+        for tt in kinds if cid.startswith("all") else kinds[cid == "rot":][:1]:
+            f1, f2 = t.g.fixed[tt[0]] == 0, t.g.fixed[tt[1]] == 0
+            assert (f1 & f2).any() and (f1 ^ f2).any() and (~f1 & ~f2).any()
+
+
+def test_numpy_tether_errors_restate_the_oracle():
+    t = B.tcase("all-kinds")
+    ob = B.make_oracle(t.g, t.tethers)
+    qt = ob.state()[0]
+    i = 0
+    for kind, tt in enumerate((t.tethers.distance, t.tethers.rotation)):
+        for a, b, p, w in zip(*tt):
+            e = ob.tether_linearization(i)[0]
+            i += 1
+            if len(e):
+                assert abs(B.tether_error_numpy(kind, qt[a], qt[b], p, w) - e[0]) <= 64 * B.EPS * max(1.0, abs(e[0]))
+
+
+@pytest.mark.parametrize("cid", B.FD_CASE_IDS)
+def test_fd_tolerance_factor(cid):
+    """F of ba_cases.FD_F is 4 x the spread of independent fp64 roundings of the 1e-9 quotient, in
+    units of d_fd (rounded up, not inflated), and the hp Jacobian agrees with the oracle's quotient
+    to the noise of the latter."""
+    t = B.tcase(cid)
+    r = B.fd_sample_ratios(cid)
+    print(f"{cid}: d_fd {t.d_fd:.3g} = {t.d_fd / t.tight:.3g} state_tol; samples / d_fd "
+          + " ".join(f"{k} {v:.3f}" for k, v in r.items()) + f"; F {B.FD_F[cid]}")
+    assert r["oracle"] == 1.0
+    assert 4 * max(r.values()) <= B.FD_F[cid] <= 1.02 * 4 * max(r.values())
+    hp = {b.index: b for b in B.tether_blocks(t.g, t.tethers, t.points_fixed, "hp")}
+    for b in B.tether_blocks(t.g, t.tethers, t.points_fixed):
+        if b.kind < 2:
+            for J, Jh in ((b.J1, hp[b.index].J1), (b.J2, hp[b.index].J2)):
+                assert np.abs(J - Jh).max() <= 2e-5  # eps |e| / 1e-9 with |e| < 10, and some
+
+
+# ---- mutation checks of the tether comparison --------------------------------------------------
+def _only(index, **kw):
+    def mutate(blocks):
+        hit = [b for b in blocks if b.index == index]
+        assert len(hit) == 1
+        for k, v in kw.items():
+            setattr(hit[0], k, v)
+    return mutate
+
+
+def _drop(index):
+    def mutate(blocks):
+        n = len(blocks)
+        blocks[:] = [b for b in blocks if b.index != index]
+        assert len(blocks) == n - 1
+    return mutate
+
+
+def _huberised(delta):
+    def mutate(blocks):
+        hit = 0
+        for b in blocks:
+            chi2 = b.om * float(b.e @ b.e)
+            if chi2 > delta * delta:
+                b.scale = delta / np.sqrt(chi2)
+                hit += 1
+        assert hit > 0
+    return mutate
+
+
+def _scaled_distance_entry(rel):
+    def mutate(blocks):
+        b = next(b for b in blocks if b.kind == 0 and np.abs(b.J1).max() > 0)
+        b.J1[0, int(np.argmax(np.abs(b.J1[0])))] *= 1.0 + rel
+    return mutate
+
+
+# (case, mutation name) -> (mutation, does the 1e-4 pose comparison accept the mutated reference)
+TETHER_MUTATIONS = {
+    ("tr-mixed", "H12 transposed on the c1 > c2 tether"): (_only(B.TR_MIXED_REVERSED, transpose12=True), True),
+    ("tr-mixed", "second tether of the doubled pair dropped"): (_drop(B.TR_MIXED_DOUBLED_SECOND), True),
+    ("tr-mixed", "second tether's H12 overwrites the first's"): (_only(B.TR_MIXED_DOUBLED_SECOND - 1, h12=False), False),
+    ("tr-mixed", "a transform weight times 1 + 1e-6"): (_only(0, scale=1.0 + 1e-6), True),
+    ("pf-tr", "a transform weight times 1 + 1e-6"): (_only(0, scale=1.0 + 1e-6), True),
+    ("tr-huber", "tethers Huber-robustified"): (_huberised(1.8), False),
+    ("pf-huber", "tethers Huber-robustified"): (_huberised(0.9), True),
+    ("dist", "a distance Jacobian entry times 1 + 1e-4"): (_scaled_distance_entry(1e-4), True),
+    ("all-kinds", "a distance Jacobian entry times 1 + 1e-4"): (_scaled_distance_entry(1e-4), True),
+    ("all-kinds-41", "a distance Jacobian entry times 1 + 1e-4"): (_scaled_distance_entry(1e-4), True),
+    ("all-kinds-pf", "a distance Jacobian entry times 1 + 1e-4"): (_scaled_distance_entry(1e-4), True),
+}
+
+
+@pytest.mark.parametrize("cid,name", list(TETHER_MUTATIONS))
+def test_comparison_rejects_a_wrong_tether_block(cid, name):
+    """A reference with one tether block slightly wrong must miss the case's tolerance when held
+    against the oracle's state; the last column of TETHER_MUTATIONS says whether the 1e-4 pose
+    comparison after one trial accepts it."""
+    mutate, old_net_accepts = TETHER_MUTATIONS[cid, name]
+    t = B.tcase(cid)
+    ob, _ = B.oracle_one_trial(t.g, t.lam, t.huber, t.tethers, t.points_fixed)
+    so = ob.state()
+    m = t.dense(jac="hp" if B.TCASES[cid].fd else "oracle", mutate=mutate)
+    mut = (m.qt, m.xyz)
+    ratio = B.state_diff(so, mut) / t.tol
+    try:
+        compare(_State(so), _State(mut))
+        accepted = True
+    except AssertionError:
+        accepted = False
+    print(f"{cid}: {name}: difference / tolerance {ratio:.3g}, 1e-4 comparison accepts: {accepted}")
+    assert ratio > 1, ratio
+    assert accepted == old_net_accepts

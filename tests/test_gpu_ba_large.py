@@ -5,7 +5,8 @@
     state_tol = 4 eps (cond2(S) max|dx| + max|state|): 1 to 96 free cameras, both sides of the 40/41
     kernel switch, block counts without padding rows, Huber-weighted systems, scattered and
     block-diagonal S, fixed cameras between free ones.  The CPU side of the same comparison and
-    its preconditions are in test_ba_dense_reference.py.
+    its preconditions are in test_ba_dense_reference.py; the same trial with tethers, fixed
+    points and odd edge lists is in test_gpu_ba_onetrial.py.
 (b) The in-place solver (np > 240: S cleared per trial, factored in place) over several steps with
     rejected trials, speculative linearisation, outlier removal, a camera leaving the system, and one
     instance crossing the switch in both directions; envelope fill from a far off-band block.
