@@ -442,6 +442,226 @@ inline std::vector<MapPointKeyframeAssociations> NewMapPointsCreation(
     return out;
 }
 
+// What the mapping task's cheap loop closure reads of the settings: LoopClosureSettings
+// (MageSettings.h:197-207) with its CheapLoopClosureMatchingSettings, TrackLocalMapSettings' view
+// angle and OrbMatcherSettings (:180-194), and the keyframes' image border, size and pyramid.
+struct CheapLoopClosureSettings {
+    unsigned MaxMapPoints{200}, MinKeyframe{10};
+    float MatchSearchRadius{18.f};
+    float MinDegreesBetweenCurrentViewAndMapPointView{60.f};
+    float ImageBorder{7.5f};
+    unsigned ImageWidth{640}, ImageHeight{480};
+    unsigned NumLevels{1};
+    float PyramidScale{1.5f};
+    int CheapLoopClosureMaxHammingDistance{30}, CheapLoopClosureMinHammingDifference{1};
+    int ConnectMaxHammingDistance{30}, ConnectMinHammingDifference{1};
+
+    mage_loop_closure_settings ToC() const
+    {
+        mage_loop_closure_settings s{};
+        s.struct_size = (uint32_t)sizeof(s);
+        s.max_map_points = MaxMapPoints;
+        s.min_keyframes = MinKeyframe;
+        s.search_radius = MatchSearchRadius;
+        s.min_view_degrees = MinDegreesBetweenCurrentViewAndMapPointView;
+        s.image_border = ImageBorder;
+        s.width = ImageWidth;
+        s.height = ImageHeight;
+        s.num_levels = NumLevels;
+        s.pyramid_scale = PyramidScale;
+        s.closure_max_hamming_distance = CheapLoopClosureMaxHammingDistance;
+        s.closure_min_hamming_difference = CheapLoopClosureMinHammingDifference;
+        s.connect_max_hamming_distance = ConnectMaxHammingDistance;
+        s.connect_min_hamming_difference = ConnectMinHammingDifference;
+        return s;
+    }
+};
+
+using MapPointObservation = mage_map_point_obs;  // one entry of MapPoint::m_keyframes, as the refresh reads it
+using MapPointState = mage_map_point_state;
+
+// A map point as the step reads it: its derived state and its observations in m_keyframes' order.
+struct MapPointView {
+    MapPointState State{};
+    std::vector<MapPointObservation> Observations;
+};
+
+// MapPoint::UpdateRepresentativeDescriptor and UpdateMeanViewDirectionAndDistances (Map/MapPoint.cpp:
+// 80-155) for a point at `position` with the given observations.  device < 0 runs the CPU backend.
+inline MapPointState UpdateMapPoint(const CheapLoopClosureSettings& settings, const std::array<float, 3>& position,
+                                    const std::vector<MapPointObservation>& observations, int device = 0)
+{
+    const mage_loop_closure_settings s = settings.ToC();
+    const uint32_t n = (uint32_t)observations.size();
+    const MapPointObservation none{};
+    MapPointState state{};
+    const MapPointObservation* obs = n ? observations.data() : &none;
+    if (device < 0)
+        check(mage_map_points_refresh_host(&s, 1, position.data(), obs, std::max(n, 1u), &n, &state));
+    else
+        check(mage_map_points_refresh(&s, 1, position.data(), obs, std::max(n, 1u), &n, &state, device));
+    return state;
+}
+
+// What the step reads of a keyframe on top of KeyframeView: its id, the descriptors, and per keypoint
+// the index of the map point it is associated with, or -1 (HasMapPoint / IsAssociatedToMapPoint and,
+// for the new keyframe, the unassociated mask).  UnassociatedKeypointMask (covisible keyframes;
+// CreateUnassociatedMask) is updated in place.
+struct LoopClosureKeyframe {
+    int Id{0};
+    KeyframeView View;
+    const std::vector<Descriptor>* Descriptors{nullptr};
+    const std::vector<int32_t>* KeypointMapPoints{nullptr};
+    std::vector<bool>* UnassociatedKeypointMask{nullptr};
+};
+
+struct LoopClosureAssociation {
+    uint32_t MapPoint;  // index into the map
+    uint32_t Keypoint;
+};
+
+struct CheapLoopClosureResult {
+    std::vector<LoopClosureAssociation> Associations;             // CheapLoopClosure's return value
+    std::vector<std::vector<LoopClosureAssociation>> Connected;   // per covisible keyframe, TryConnectMapPoints' extraAssociations
+    std::vector<bool> Modified;                                   // modifiedKeyframes: UpdateGraph is the caller's
+    std::vector<uint32_t> Sample;                                 // GetSampleOfMapPoints, as map indices
+    std::vector<mage_loop_closure_assoc> ClosureRecords, ConnectRecords;  // by place in the sample (x n_kf)
+    std::vector<uint8_t> ClosureVerdicts, ConnectVerdicts;        // MAGE_LC_*
+};
+
+// MappingWorker.cpp:160-181: CheapLoopClosure (:20-73) of the map's sample into the new keyframe Ki,
+// InsertKeyframe's associations (ThreadSafeMap.cpp:242-249) and TryConnectMapPoints (:715-787) over
+// the covisible keyframes in the given order.  The associated map points gain their observations and
+// are refreshed in `map`; the covisible keyframes' masks are updated.  `loopCounter` is the mapping
+// task's frame counter, `keyframeCount` the map's GetKeyframesCount().  device < 0 runs the CPU
+// backend.  Throws Error (MAGE_EUNSUPPORTED) for a keyframe with more than 4096 keypoints.
+inline CheapLoopClosureResult CheapLoopClosureAndConnect(const CheapLoopClosureSettings& settings,
+                                                         std::vector<MapPointView>& map, uint32_t loopCounter,
+                                                         uint32_t keyframeCount, const LoopClosureKeyframe& Ki,
+                                                         const std::vector<LoopClosureKeyframe>& covisibleKeyframes,
+                                                         int device = 0)
+{
+    const mage_loop_closure_settings s = settings.ToC();
+    const uint32_t n_kf = (uint32_t)covisibleKeyframes.size(), n_map = (uint32_t)map.size(), max = settings.MaxMapPoints;
+    size_t pitch = 0;
+    for (const MapPointView& p : map) {
+        if ((size_t)p.State.n_obs != p.Observations.size()) throw std::invalid_argument("State.n_obs must count the observations");
+        pitch = std::max(pitch, p.Observations.size());
+    }
+    pitch += 1 + (size_t)n_kf;  // room for every association the step can make
+    std::vector<MapPointState> state(n_map);
+    std::vector<MapPointObservation> obs((size_t)n_map * pitch);
+    for (uint32_t i = 0; i < n_map; i++) {
+        state[i] = map[i].State;
+        std::copy(map[i].Observations.begin(), map[i].Observations.end(), obs.begin() + (size_t)i * pitch);
+    }
+    auto lengths = [](const LoopClosureKeyframe& kf) {
+        const size_t nk = kf.View.KeyPoints->size();
+        if (!kf.Descriptors || !kf.KeypointMapPoints || kf.Descriptors->size() != nk || kf.KeypointMapPoints->size() != nk)
+            throw std::invalid_argument("a keyframe's keypoints, descriptors and map points must have one length");
+        return nk;
+    };
+    const size_t n_ki = lengths(Ki);
+    std::vector<uint8_t> ki_desc;
+    for (const Descriptor& d : *Ki.Descriptors) ki_desc.insert(ki_desc.end(), d.begin(), d.end());
+    std::vector<float> pos, rot, intr;
+    std::vector<KeyPoint> kps;
+    std::vector<uint8_t> desc, mask;
+    std::vector<int32_t> point, ids(n_kf);
+    std::vector<uint32_t> start(n_kf + 1, 0);
+    for (uint32_t k = 0; k < n_kf; k++) {
+        const LoopClosureKeyframe& kf = covisibleKeyframes[k];
+        if (!kf.UnassociatedKeypointMask || kf.UnassociatedKeypointMask->size() != lengths(kf))
+            throw std::invalid_argument("a covisible keyframe needs its unassociated mask");
+        pos.insert(pos.end(), kf.View.Position.begin(), kf.View.Position.end());
+        rot.insert(rot.end(), kf.View.Rotation.begin(), kf.View.Rotation.end());
+        intr.insert(intr.end(), kf.View.Intrinsics.begin(), kf.View.Intrinsics.end());
+        kps.insert(kps.end(), kf.View.KeyPoints->begin(), kf.View.KeyPoints->end());
+        for (const Descriptor& d : *kf.Descriptors) desc.insert(desc.end(), d.begin(), d.end());
+        point.insert(point.end(), kf.KeypointMapPoints->begin(), kf.KeypointMapPoints->end());
+        mask.insert(mask.end(), kf.UnassociatedKeypointMask->begin(), kf.UnassociatedKeypointMask->end());
+        start[k + 1] = (uint32_t)kps.size();
+        ids[k] = kf.Id;
+    }
+    CheapLoopClosureResult r;
+    r.Sample.resize(max);
+    r.ClosureRecords.resize(max);
+    r.ClosureVerdicts.assign(max, 0xFF);
+    r.ConnectRecords.resize(std::max<size_t>((size_t)max * n_kf, 1));
+    r.ConnectVerdicts.assign(std::max<size_t>((size_t)max * n_kf, 1), 0xFF);
+    std::vector<uint8_t> ki_mask(std::max<size_t>(n_ki, 1)), modified(std::max<uint32_t>(n_kf, 1));
+    uint32_t counts[3] = {0, 0, 0}, status = 0;
+    mage_loop_closure_problem p{};
+    p.struct_size = (uint32_t)sizeof(p);
+    p.n_map = n_map;
+    p.state = state.data();
+    p.obs = obs.data();
+    p.obs_pitch = (int64_t)pitch;
+    p.offset = loopCounter;
+    p.n_keyframes = keyframeCount;
+    p.ki_id = Ki.Id;
+    p.n_ki = (uint32_t)n_ki;
+    p.ki_pos3 = Ki.View.Position.data();
+    p.ki_r9 = Ki.View.Rotation.data();
+    p.ki_intr4 = Ki.View.Intrinsics.data();
+    p.ki_kp = Ki.View.KeyPoints->data();
+    p.ki_desc = ki_desc.data();
+    p.ki_point = Ki.KeypointMapPoints->data();
+    p.n_kf = n_kf;
+    p.kf_id = ids.data();
+    p.kf_pos3 = pos.data();
+    p.kf_r9 = rot.data();
+    p.kf_intr4 = intr.data();
+    p.kf_kp = kps.data();
+    p.kf_desc = desc.data();
+    p.kf_point = point.data();
+    p.kf_start = start.data();
+    p.kf_mask = mask.data();
+    p.sample_index = r.Sample.data();
+    p.closure = r.ClosureRecords.data();
+    p.closure_verdict = r.ClosureVerdicts.data();
+    p.connect = r.ConnectRecords.data();
+    p.connect_verdict = r.ConnectVerdicts.data();
+    p.ki_mask = ki_mask.data();
+    p.kf_modified = modified.data();
+    p.counts = counts;
+    p.status = &status;
+    check(device < 0 ? mage_cheap_loop_closure_host(&s, &p) : mage_cheap_loop_closure(&s, &p, device));
+    if (status & MAGE_LC_STATUS_OVER_LIMIT) throw Error(MAGE_EUNSUPPORTED, "more than 4096 keypoints in a keyframe");
+    const uint32_t L = counts[0];
+    r.Sample.resize(L);
+    r.ClosureRecords.resize(L);
+    r.ClosureVerdicts.resize(L);
+    r.ConnectRecords.resize((size_t)L * n_kf);
+    r.ConnectVerdicts.resize((size_t)L * n_kf);
+    r.Connected.assign(n_kf, {});
+    r.Modified.assign(n_kf, false);
+    for (uint32_t j = 0; j < L; j++) {
+        const uint32_t i = r.Sample[j];
+        if (r.ClosureRecords[j].keypoint >= 0) r.Associations.push_back({i, (uint32_t)r.ClosureRecords[j].keypoint});
+        for (uint32_t k = 0; k < n_kf; k++)
+            if (r.ConnectRecords[(size_t)j * n_kf + k].keypoint >= 0)
+                r.Connected[k].push_back({i, (uint32_t)r.ConnectRecords[(size_t)j * n_kf + k].keypoint});
+        map[i].State = state[i];
+        map[i].Observations.assign(obs.begin() + (size_t)i * pitch, obs.begin() + (size_t)i * pitch + state[i].n_obs);
+    }
+    if (L)
+        for (uint32_t k = 0; k < n_kf; k++) {
+            r.Modified[k] = modified[k] != 0;
+            for (uint32_t t = start[k]; t < start[k + 1]; t++)
+                (*covisibleKeyframes[k].UnassociatedKeypointMask)[t - start[k]] = mask[t] != 0;
+        }
+    return r;
+}
+
+// CheapLoopClosure (MappingWorker.cpp:20-73) with InsertKeyframe's associations alone.
+inline CheapLoopClosureResult CheapLoopClosure(const CheapLoopClosureSettings& settings, std::vector<MapPointView>& map,
+                                               uint32_t loopCounter, uint32_t keyframeCount, const LoopClosureKeyframe& Ki,
+                                               int device = 0)
+{
+    return CheapLoopClosureAndConnect(settings, map, loopCounter, keyframeCount, Ki, {}, device);
+}
+
 // StereoMapInitializationSettings (MageSettings.h:135-147) with its OrbMatcherSettings and
 // BundleAdjustSettings bags (:36-52).
 struct StereoMapInitializationSettings {

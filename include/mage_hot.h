@@ -595,6 +595,254 @@ mage_status mage_new_points_associate_batch_device(const mage_new_points_setting
                                                    uint32_t* d_status, mage_stream stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Cheap loop closure — the map-point refresh after an association                              */
+/* (Core/.../Source/Map/MapPoint.cpp:35-46, 80-155)                                            */
+/* ------------------------------------------------------------------------------------------ */
+
+/* What the mapping task's CheapLoopClosure (Tasks/MappingWorker.cpp:20-73) and TryConnectMapPoints
+ * (Map/ThreadSafeMap.cpp:715-787) read of the settings: LoopClosureSettings (MageSettings.h:197-207),
+ * TrackLocalMapSettings' view angle and matcher (:180-194), the keyframe's image border and size and
+ * the pyramid.  struct_size must be sizeof(mage_loop_closure_settings); anything else is
+ * MAGE_EINVAL.  The refresh entries below read num_levels and pyramid_scale; the other fields are
+ * checked and belong to the closure and connect steps. */
+typedef struct mage_loop_closure_settings {
+    uint32_t struct_size;
+    uint32_t max_map_points;  /* LoopClosureSettings.MaxMapPoints 200, in 1..1024 */
+    uint32_t min_keyframes;   /* LoopClosureSettings.MinKeyframe 10 */
+    float search_radius;      /* LoopClosureSettings.MatchSearchRadius 18 (pixels), >= 0 */
+    float min_view_degrees;   /* TrackLocalMapSettings.MinDegreesBetweenCurrentViewAndMapPointView 60 */
+    float image_border;       /* GetImageBorder(); the gate uses border - search_radius / 2 (MappingWorker.cpp:45) */
+    uint32_t width, height;   /* image size, positive */
+    uint32_t num_levels;      /* pyramid levels, in 1..8 */
+    float pyramid_scale;      /* pyramid scale, > 1 */
+    int32_t closure_max_hamming_distance;   /* CheapLoopClosureMatchingSettings.MaxHammingDistance 30, in [-1, 256] */
+    int32_t closure_min_hamming_difference; /* CheapLoopClosureMatchingSettings.MinHammingDifference 1 */
+    int32_t connect_max_hamming_distance;   /* TrackLocalMapSettings.OrbMatcherSettings.MaxHammingDistance 30 */
+    int32_t connect_min_hamming_difference; /* TrackLocalMapSettings.OrbMatcherSettings.MinHammingDifference 1 */
+} mage_loop_closure_settings;
+
+/* One observation of a map point: what MapPoint's refresh reads of the observing keyframe.  The
+ * descriptor comes first and the record is 16-byte aligned, so a device list of them can be read
+ * with 16-byte loads.  64 bytes. */
+typedef struct mage_map_point_obs {
+    uint8_t desc[32];    /* the associated keypoint's descriptor */
+    float centre[3];     /* the keyframe's GetWorldSpacePosition() */
+    int32_t octave;      /* the associated keypoint's octave */
+    int32_t keyframe_id; /* carried, not read */
+    uint32_t reserved[3];
+} mage_map_point_obs;
+
+/* A map point's derived state.  rep is the index, in the point's observation list, of
+ * m_representativeDescriptorKeyframe, or -1 for a point without observations.  40 bytes. */
+typedef struct mage_map_point_state {
+    float pos[3];  /* m_position */
+    float mvd[3];  /* m_meanViewingDirection */
+    float dmin, dmax;
+    int32_t rep;
+    int32_t n_obs;
+} mage_map_point_state;
+
+#define MAGE_MP_MAX_OBS 65536 /* observations of one point: the summed distance stays exact in float */
+
+/* MapPoint::UpdateRepresentativeDescriptor and UpdateMeanViewDirectionAndDistances (MapPoint.cpp:
+ * 80-155) for n_points points, as AddKeyframeAssociation (:35-46) runs them after every new
+ * association.  Point i has position positions[3 i .. 3 i + 2] and observations obs[i * obs_pitch ..
+ * i * obs_pitch + n_obs[i]), in the order of m_keyframes.
+ *   rep   -1 for no observation; otherwise the observation with the first strictly smallest sum of
+ *         Hamming distances to all of the point's observations, itself included (:105-125; the
+ *         reference sums in float, which is exact below 65536 observations).
+ *   mvd   {0, 0, 0} for no observation; otherwise Normalize of the sum, from {0, 0, 0} and in
+ *         observation order, of Normalize(pos - centre) (:141-146).  Normalize as Utils/cv.h:
+ *         287-296: a zero-length vector is left as it is; the norm is sqrtf of the float dot
+ *         product and the division multiplies by the float reciprocal, as the tracker's
+ *         one-keyframe case does.
+ *   dmax, dmin   |centre_rep - pos| times ComputeDMax's / ComputeDMin's factor of the representative
+ *         keypoint's octave (Map/MappingMath.h:32-40; the octave is clamped to the tables' 0..7).
+ *         0 for no observation (the reference keeps the values it had).
+ * state[i] also gets pos and n_obs.  obs_pitch must be in 1..MAGE_MP_MAX_OBS and no n_obs[i] may
+ * exceed it (MAGE_EINVAL, nothing written).  n_points == 0 returns MAGE_OK.  Plain C++ on the
+ * calling thread: the CPU backend, bit-identical to the kernel.  No GPU. */
+mage_status mage_map_points_refresh_host(const mage_loop_closure_settings* settings, uint32_t n_points,
+                                         const float* positions, const mage_map_point_obs* obs, int64_t obs_pitch,
+                                         const uint32_t* n_obs, mage_map_point_state* state);
+
+/* The same on the GPU.  Host buffers, synchronous, runs on `device`. */
+mage_status mage_map_points_refresh(const mage_loop_closure_settings* settings, uint32_t n_points,
+                                    const float* positions, const mage_map_point_obs* obs, int64_t obs_pitch,
+                                    const uint32_t* n_obs, mage_map_point_state* state, int device);
+
+/* Device buffers, one wave per point, asynchronous on `stream`.  d_obs must be 16-byte aligned.  A
+ * point whose count exceeds obs_pitch sets bit 0 of *d_status and its state is left untouched; the
+ * other points are unaffected.  *d_status is only ever ORed into. */
+mage_status mage_map_points_refresh_batch_device(const mage_loop_closure_settings* settings, uint32_t n_points,
+                                                 const float* d_positions, const mage_map_point_obs* d_obs,
+                                                 int64_t obs_pitch, const uint32_t* d_n_obs,
+                                                 mage_map_point_state* d_state, uint32_t* d_status,
+                                                 mage_stream stream);
+
+/* What one sampled point found in one keyframe: the projection (ProjectUndistorted), the predicted
+ * octave and the keypoint it was associated with, or -1.  A field the reference had not computed
+ * when it skipped or refused the pair is 0 (x, y, octave) or -1 (keypoint), by the rule of
+ * mage_new_point_assoc: x and y are 0 for NOT_SAMPLED and HAS_POINT, octave is 0 up to and
+ * including DISTANCE.  16 bytes. */
+typedef struct mage_loop_closure_assoc {
+    float x, y;
+    int32_t octave;
+    int32_t keypoint;
+} mage_loop_closure_assoc;
+
+/* Verdict of a (sampled point, keyframe) pair: the reference's first reason, in its order. */
+#define MAGE_LC_ASSOCIATED 0  /* extraAssociations.emplace_back (MappingWorker.cpp:67, ThreadSafeMap.cpp:764) */
+#define MAGE_LC_NOT_SAMPLED 1 /* connect stage: the closure did not associate the point, so TryConnectMapPoints is not given it */
+#define MAGE_LC_HAS_POINT 2   /* HasMapPoint / IsAssociatedToMapPoint (MappingWorker.cpp:51, ThreadSafeMap.cpp:752) */
+#define MAGE_LC_BEHIND 3      /* IsGoodCandidate: depth < 0 (TrackLocalMap.cpp:529) */
+#define MAGE_LC_BORDER 4      /* IsGoodCandidate: outside the image less the border (:529) */
+#define MAGE_LC_ANGLE 5       /* IsGoodCandidate: mean view direction . forward < cos(min view degrees) (:541) */
+#define MAGE_LC_DISTANCE 6    /* IsGoodCandidate: outside [dMin, dMax] (:549) */
+#define MAGE_LC_OCTAVE 7      /* predicted octave < 0 or > numLevels (:365; the test is >, not >=) */
+#define MAGE_LC_NO_MATCH 8    /* MatchMapPointToCurrentFrame found nothing (:375), or the point has no descriptor */
+
+#define MAGE_LC_STATUS_OVER_LIMIT 1u /* a keyframe has more than 4096 keypoints (batch form: or exceeds its pitch / slots) */
+#define MAGE_LC_STATUS_OBS_FULL 2u   /* a sampled point's observation list cannot hold n_obs + 1 + n_kf entries */
+
+/* One mapping task's CheapLoopClosure (Tasks/MappingWorker.cpp:20-73), InsertKeyframe's effect on
+ * the points it associated (Map/ThreadSafeMap.cpp:242-249, MapPoint.cpp:35-46) and
+ * TryConnectMapPoints (ThreadSafeMap.cpp:715-787), MappingWorker.cpp:160-181.
+ *
+ * The map: n_map points in map order, state[i] and the observation list obs[i * obs_pitch ..
+ * + state[i].n_obs) of each, both in/out; a point's descriptor is that of observation state[i].rep.
+ * Sampling (Map/Map.cpp:319-333): step = n_map / max_map_points + 1 in uint32, point i is sampled
+ * iff (offset + i + 1) % step == 0 with uint32 wrap, offset the mapping task's frame counter; the
+ * sample is cut at max_map_points.  n_keyframes is the map's keyframe count (:22).
+ *
+ * The new keyframe Ki: ki_id, pose and calibration as mage_new_points_associate takes them (pos3
+ * the view-space t, r9 the column-major R, intr4 {cx, cy, fx, fy}), n_ki keypoints with 32-byte
+ * descriptors, and ki_point[t] = the map-point index keypoint t is associated with, or -1: the
+ * unassociated mask is ki_point < 0, HasMapPoint(i) is "i appears in ki_point".  The n_kf
+ * covisible keyframes, in the order GetCovisibilityConnectedKeyframes gives them, have the same
+ * fields concatenated, keyframe k owning [kf_start[k], kf_start[k + 1]), their ids kf_id and their
+ * unassociated mask bytes kf_mask, in/out (byte != 0: available).
+ *
+ * Closure: the sampled points are offered to Ki in order; a point Ki holds is HAS_POINT; the rest go
+ * through ProjectMapPointIntoCurrentFrame (TrackLocalMap.cpp:325-388: ProjectUndistorted,
+ * IsGoodCandidate :519-554 with border = image_border - search_radius / 2 and the angle
+ * min_view_degrees, ComputeOctave, then the single-query RadiusMatch of search_radius under the
+ * closure matcher pair); a success takes the keypoint for every later point.  Every associated point
+ * then gains {Ki's descriptor and octave at the keypoint, Ki's centre, ki_id} as its last
+ * observation and is refreshed as mage_map_points_refresh does.
+ * Connect: the covisible keyframes are visited in order; in each, the points the closure associated
+ * are visited in order, a point the keyframe holds is HAS_POINT, the others go through
+ * ProjectMapPointIntoCurrentFrame with their CURRENT state under the connect matcher pair, successes
+ * clearing the keyframe's mask as they happen; after the keyframe's loop each success is appended
+ * to its point's observations and the point refreshed, before the next keyframe is visited.
+ *
+ * Outputs, j the place in the sample: sample_index[j] the map index; closure[j] and
+ * closure_verdict[j]; connect[j * n_kf + k] and connect_verdict[j * n_kf + k] (NOT_SAMPLED for a
+ * point the closure did not associate); ki_mask[t] Ki's mask after the closure (n_ki bytes, out);
+ * kf_modified[k] whether keyframe k gained an association (UpdateGraph is the caller's);
+ * counts = {sampled, associated by the closure, associated by the connect stage}.
+ * *status: MAGE_LC_STATUS_OVER_LIMIT when a keyframe has more than 4096 keypoints — that keyframe
+ * is left untouched (its verdict bytes and mask unchanged, its records {0, 0, 0, -1}, no
+ * association), the others unaffected; MAGE_LC_STATUS_OBS_FULL when obs_pitch cannot hold
+ * n_obs + 1 + n_kf observations for some sampled point — the problem is refused whole before
+ * anything but counts (zero) and status is written, and the synchronous forms return
+ * MAGE_ECAPACITY.  n_keyframes < min_keyframes gives zero counts and writes nothing else.
+ * n_kf == 0 runs the closure alone.  struct_size must be sizeof(mage_loop_closure_problem). */
+typedef struct mage_loop_closure_problem {
+    uint32_t struct_size;
+    uint32_t n_map;
+    mage_map_point_state* state;
+    mage_map_point_obs* obs;
+    int64_t obs_pitch;
+    uint32_t offset;
+    uint32_t n_keyframes;
+    int32_t ki_id;
+    uint32_t n_ki;
+    const float *ki_pos3, *ki_r9, *ki_intr4;
+    const mage_keypoint* ki_kp;
+    const uint8_t* ki_desc;
+    const int32_t* ki_point;
+    uint32_t n_kf;
+    uint32_t reserved;
+    const int32_t* kf_id;
+    const float *kf_pos3, *kf_r9, *kf_intr4;
+    const mage_keypoint* kf_kp;
+    const uint8_t* kf_desc;
+    const int32_t* kf_point;
+    const uint32_t* kf_start;
+    uint8_t* kf_mask;
+    uint32_t* sample_index;            /* max_map_points */
+    mage_loop_closure_assoc* closure;  /* max_map_points */
+    uint8_t* closure_verdict;          /* max_map_points */
+    mage_loop_closure_assoc* connect;  /* max_map_points * n_kf */
+    uint8_t* connect_verdict;          /* max_map_points * n_kf */
+    uint8_t* ki_mask;                  /* n_ki */
+    uint8_t* kf_modified;              /* n_kf */
+    uint32_t* counts;                  /* 3 */
+    uint32_t* status;                  /* 1 */
+} mage_loop_closure_problem;
+
+/* Plain C++ on the calling thread, the reference's literal nested loops: the CPU backend,
+ * bit-identical to the kernels.  No GPU. */
+mage_status mage_cheap_loop_closure_host(const mage_loop_closure_settings* settings,
+                                         const mage_loop_closure_problem* problem);
+
+/* The same on the GPU.  Host buffers, synchronous, runs on `device`. */
+mage_status mage_cheap_loop_closure(const mage_loop_closure_settings* settings,
+                                    const mage_loop_closure_problem* problem, int device);
+
+/* Batched device form: `problems` independent mapping tasks, three launches chained on `stream`
+ * (closure, its refresh, connect) with no host step.  Map arrays advance by map_pitch points
+ * (observations by map_pitch * obs_pitch) per problem, Ki arrays by ki_pitch keypoints (poses 3 / 9
+ * / 4 floats), covisible keyframe arrays per pair = problem * kf_slots + k by kf_pitch keypoints;
+ * problem i uses its first d_n_kf[i] pairs.  Per problem: d_sample_index, d_closure and
+ * d_closure_verdict at problem * max_map_points, d_connect and d_connect_verdict at ((problem *
+ * max_map_points) + j) * kf_slots + k, d_ki_mask at problem * ki_pitch, d_kf_modified at pair,
+ * d_counts at problem * 3, d_status at problem.  Nothing is written beyond the counts.
+ * MAGE_LC_STATUS_OVER_LIMIT also for a keypoint count over its pitch; a problem with n_map >
+ * map_pitch or d_n_kf > kf_slots is refused whole with that bit (zero counts).  Descriptor and
+ * observation pointers must be 16-byte aligned.  struct_size must be
+ * sizeof(mage_loop_closure_batch). */
+typedef struct mage_loop_closure_batch {
+    uint32_t struct_size;
+    uint32_t problems;
+    uint32_t kf_slots;
+    uint32_t reserved;
+    int64_t map_pitch, obs_pitch, ki_pitch, kf_pitch;
+    const uint32_t* d_n_map;
+    mage_map_point_state* d_state;
+    mage_map_point_obs* d_obs;
+    const uint32_t* d_offset;
+    const uint32_t* d_n_keyframes;
+    const int32_t* d_ki_id;
+    const uint32_t* d_n_ki;
+    const float *d_ki_pos3, *d_ki_r9, *d_ki_intr4;
+    const mage_keypoint* d_ki_kp;
+    const uint8_t* d_ki_desc;
+    const int32_t* d_ki_point;
+    const uint32_t* d_n_kf;
+    const int32_t* d_kf_id;
+    const float *d_kf_pos3, *d_kf_r9, *d_kf_intr4;
+    const mage_keypoint* d_kf_kp;
+    const uint8_t* d_kf_desc;
+    const int32_t* d_kf_point;
+    const uint32_t* d_n_kf_kp;
+    uint8_t* d_kf_mask;
+    uint32_t* d_sample_index;
+    mage_loop_closure_assoc* d_closure;
+    uint8_t* d_closure_verdict;
+    mage_loop_closure_assoc* d_connect;
+    uint8_t* d_connect_verdict;
+    uint8_t* d_ki_mask;
+    uint8_t* d_kf_modified;
+    uint32_t* d_counts;
+    uint32_t* d_status;
+} mage_loop_closure_batch;
+
+mage_status mage_cheap_loop_closure_batch_device(const mage_loop_closure_settings* settings,
+                                                 const mage_loop_closure_batch* batch, mage_stream stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Stereo map initialisation — the device stage of StereoMapInit::Initialize                   */
 /* (Core/.../Source/Stereo/StereoMapInit.cpp:97-194)                                           */
 /* ------------------------------------------------------------------------------------------ */

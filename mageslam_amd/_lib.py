@@ -53,6 +53,8 @@ EXPORTS = [
     "mage_bounding_plane_depths_host", "mage_bounding_plane_depths", "mage_bounding_plane_depths_batch_device",
     "mage_voi_settings_prepare", "mage_voi_teardrop_host", "mage_volume_of_interest_host", "mage_volume_of_interest",
     "mage_volume_of_interest_scratch_bytes", "mage_volume_of_interest_batch_device",
+    "mage_map_points_refresh_host", "mage_map_points_refresh", "mage_map_points_refresh_batch_device",
+    "mage_cheap_loop_closure_host", "mage_cheap_loop_closure", "mage_cheap_loop_closure_batch_device",
 ]
 
 
@@ -238,6 +240,55 @@ class VoiSettingsC(C.Structure):
         return cls(struct_size=C.sizeof(cls), **kw)
 
 
+class LoopClosureSettingsC(C.Structure):
+    """mage_loop_closure_settings (include/mage_hot.h); struct_size is filled in by make()."""
+    _fields_ = [("struct_size", C.c_uint32), ("max_map_points", C.c_uint32), ("min_keyframes", C.c_uint32),
+                ("search_radius", C.c_float), ("min_view_degrees", C.c_float), ("image_border", C.c_float),
+                ("width", C.c_uint32), ("height", C.c_uint32), ("num_levels", C.c_uint32), ("pyramid_scale", C.c_float),
+                ("closure_max_hamming_distance", C.c_int32), ("closure_min_hamming_difference", C.c_int32),
+                ("connect_max_hamming_distance", C.c_int32), ("connect_min_hamming_difference", C.c_int32)]
+
+    @classmethod
+    def make(cls, **kw):
+        return cls(struct_size=C.sizeof(cls), **kw)
+
+
+class _PointerArgs(C.Structure):
+    """An argument block whose _POINTERS fields take anything ptr() takes; struct_size is filled in
+    by make()."""
+    _POINTERS = ()
+
+    @classmethod
+    def make(cls, **kw):
+        for name in cls._POINTERS:
+            if name in kw:
+                kw[name] = ptr(kw[name])
+        return cls(struct_size=C.sizeof(cls), **kw)
+
+
+class LoopClosureProblemC(_PointerArgs):
+    """mage_loop_closure_problem (include/mage_hot.h)."""
+    _POINTERS = ("state", "obs", "ki_pos3", "ki_r9", "ki_intr4", "ki_kp", "ki_desc", "ki_point", "kf_id", "kf_pos3",
+                 "kf_r9", "kf_intr4", "kf_kp", "kf_desc", "kf_point", "kf_start", "kf_mask", "sample_index", "closure",
+                 "closure_verdict", "connect", "connect_verdict", "ki_mask", "kf_modified", "counts", "status")
+    _fields_ = ([("struct_size", C.c_uint32), ("n_map", C.c_uint32), ("state", C.c_void_p), ("obs", C.c_void_p),
+                 ("obs_pitch", C.c_int64), ("offset", C.c_uint32), ("n_keyframes", C.c_uint32), ("ki_id", C.c_int32),
+                 ("n_ki", C.c_uint32)] + [(n, C.c_void_p) for n in _POINTERS[2:8]] +
+                [("n_kf", C.c_uint32), ("reserved", C.c_uint32)] + [(n, C.c_void_p) for n in _POINTERS[8:]])
+
+
+class LoopClosureBatchC(_PointerArgs):
+    """mage_loop_closure_batch (include/mage_hot.h)."""
+    _POINTERS = ("d_n_map", "d_state", "d_obs", "d_offset", "d_n_keyframes", "d_ki_id", "d_n_ki", "d_ki_pos3", "d_ki_r9",
+                 "d_ki_intr4", "d_ki_kp", "d_ki_desc", "d_ki_point", "d_n_kf", "d_kf_id", "d_kf_pos3", "d_kf_r9",
+                 "d_kf_intr4", "d_kf_kp", "d_kf_desc", "d_kf_point", "d_n_kf_kp", "d_kf_mask", "d_sample_index",
+                 "d_closure", "d_closure_verdict", "d_connect", "d_connect_verdict", "d_ki_mask", "d_kf_modified",
+                 "d_counts", "d_status")
+    _fields_ = ([("struct_size", C.c_uint32), ("problems", C.c_uint32), ("kf_slots", C.c_uint32), ("reserved", C.c_uint32),
+                 ("map_pitch", C.c_int64), ("obs_pitch", C.c_int64), ("ki_pitch", C.c_int64), ("kf_pitch", C.c_int64)] +
+                [(n, C.c_void_p) for n in _POINTERS])
+
+
 class StereoMapInitResultC(C.Structure):
     """mage_stereo_map_init_result (include/mage_hot.h)."""
     _fields_ = [("code", C.c_int32), ("crop", C.c_int32 * 4), ("n_masked", C.c_uint32), ("n_matches", C.c_uint32),
@@ -337,6 +388,13 @@ class RelocCandidatesArgsC(C.Structure):
 
 # mage_new_point_assoc (16 B)
 NA_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("octave", "<i4"), ("keypoint", "<i4")])
+
+# mage_map_point_obs (64 B), mage_map_point_state (40 B), mage_loop_closure_assoc (16 B)
+MP_OBS_DTYPE = np.dtype([("desc", "u1", 32), ("centre", "<f4", 3), ("octave", "<i4"), ("keyframe_id", "<i4"),
+                         ("reserved", "<u4", 3)])
+MP_STATE_DTYPE = np.dtype([("pos", "<f4", 3), ("mvd", "<f4", 3), ("dmin", "<f4"), ("dmax", "<f4"), ("rep", "<i4"),
+                           ("n_obs", "<i4")])
+LC_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("octave", "<i4"), ("keypoint", "<i4")])
 
 _lib = None
 
@@ -512,6 +570,12 @@ def _declare(L: C.CDLL) -> None:
     sig("mage_volume_of_interest", st, vp, vp, vp, vp, u32, vp, u32, vp, vp, C.c_int)
     sig("mage_volume_of_interest_scratch_bytes", u64, u32, u32)
     sig("mage_volume_of_interest_batch_device", st, vp, u32, vp, i64, vp, vp, vp, u32, vp, vp, vp, vp, vp)
+    sig("mage_map_points_refresh_host", st, vp, u32, vp, vp, i64, vp, vp)
+    sig("mage_map_points_refresh", st, vp, u32, vp, vp, i64, vp, vp, C.c_int)
+    sig("mage_map_points_refresh_batch_device", st, vp, u32, vp, vp, i64, vp, vp, vp, vp)
+    sig("mage_cheap_loop_closure_host", st, vp, vp)
+    sig("mage_cheap_loop_closure", st, vp, vp, C.c_int)
+    sig("mage_cheap_loop_closure_batch_device", st, vp, vp, vp)
     sig("mage_overlap_crop_source_in_target", st, vp, vp, vp, f32, vp)
     sig("mage_stereo_map_init", st, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp, C.c_int)
     sig("mage_debug_stereo_init_host", st, vp, vp, vp, vp, vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp)

@@ -20,8 +20,8 @@ LIB = OUT / "libmage_hot.so"
 ARCH = os.environ.get("MAGE_OFFLOAD_ARCH", "gfx950")
 
 HIP_SOURCES = ["orb.hip", "match.hip", "radius.hip", "localmap.hip", "bow.hip", "ba.hip", "pose.hip", "image.hip", "track.hip", "newpoints.hip", "newpoints_assoc.hip", "stereoinit.hip",
-               "monoinit.hip", "monoinit_third.hip", "reloc_pnp.hip", "reloc_guided.hip", "scene_depth.hip", "scene_voi.hip"]
-CXX_SOURCES = ["capi.cpp", "tables.cpp", "track.cpp", "newpoints.cpp", "stereoinit.cpp", "monoinit.cpp", "monoinit_third.cpp", "reloc_pnp.cpp", "reloc_guided.cpp", "scene_depth.cpp", "scene_voi.cpp"]
+               "monoinit.hip", "monoinit_third.hip", "reloc_pnp.hip", "reloc_guided.hip", "scene_depth.hip", "scene_voi.hip", "loopclose.hip"]
+CXX_SOURCES = ["capi.cpp", "tables.cpp", "track.cpp", "newpoints.cpp", "stereoinit.cpp", "monoinit.cpp", "monoinit_third.cpp", "reloc_pnp.cpp", "reloc_guided.cpp", "scene_depth.cpp", "scene_voi.cpp", "loopclose.cpp"]
 
 COMMON = ["-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
           f"-I{PKG.parent / 'include'}"]

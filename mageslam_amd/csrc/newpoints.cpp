@@ -105,43 +105,6 @@ extern "C" mage_status mage_new_map_points_host(const mage_new_points_settings* 
 // LocallyAssociateNewAssociations (NewMapPointsCreation.cpp:337-424): the twin of
 // newpoints_assoc.hip and the CPU backend of mage_new_points_associate.
 // ------------------------------------------------------------------------------------------
-namespace {
-
-int hamming256(const uint8_t* a, const uint8_t* b)
-{
-    int d = 0;
-    for (int i = 0; i < 4; i++) {
-        uint64_t x, y;
-        std::memcpy(&x, a + 8 * i, 8);
-        std::memcpy(&y, b + 8 * i, 8);
-        d += __builtin_popcountll(x ^ y);
-    }
-    return d;
-}
-
-// The single-query RadiusMatch (FeatureMatcher.cpp:386-446) against the available keypoints, the
-// candidates in ascending keypoint index: the keypoint, or -1.
-int radius_match_one(const mage::newpoints::AssocConsts& c, float px, float py, int octave, const uint8_t* desc,
-                     const mage_keypoint* kp, const uint8_t* kdesc, uint32_t n, const uint8_t* mask)
-{
-    const float r = c.radius;
-    int best = c.max_dist + 1, second = 2147483647, train = -1;
-    for (uint32_t t = 0; t < n; t++) {
-        const float tx = kp[t].x, ty = kp[t].y;
-        if (!(tx >= px - r && tx <= px + r && ty >= py - r && ty <= py + r) || kp[t].octave != octave || !mask[t])
-            continue;
-        const int d = hamming256(desc, kdesc + 32ull * t);
-        if (d < best) {
-            train = (int)t;
-            second = best;
-            best = d;
-        }
-    }
-    return train != -1 && second - best > c.min_diff ? train : -1;
-}
-
-}  // namespace
-
 extern "C" mage_status mage_new_points_associate_host(
     const mage_new_points_settings* settings, const mage_new_points_assoc_settings* assoc, const mage_new_point* points,
     uint32_t n_points, const uint8_t* ki_desc, uint32_t n_ki, uint32_t n_kf, const float* kf_pos3, const float* kf_r9,
@@ -197,8 +160,8 @@ extern "C" mage_status mage_new_points_associate_host(
             v = project_gate(c, frames[k], kf_intr4 + 4ull * k, pt, o.x, o.y, o.octave);
             if (v != NA_NO_MATCH) continue;
             uint8_t* mask = kf_mask + kf_start[k];
-            const int t = radius_match_one(c, o.x, o.y, o.octave, ki_desc + 32ull * pt.ki_index, kf_kp + kf_start[k],
-                                           kf_desc + 32ull * kf_start[k], nk, mask);
+            const int t = host_radius_match_one(c, o.x, o.y, o.octave, ki_desc + 32ull * pt.ki_index, kf_kp + kf_start[k],
+                                                kf_desc + 32ull * kf_start[k], nk, mask);
             if (t >= 0) {
                 o.keypoint = t;
                 mask[t] = 0;

@@ -5,26 +5,20 @@
 // gate (TrackLocalMap::IsGoodCandidate), predict the octave, then the single-query RadiusMatch
 // against the keyframe's still-unassociated keypoints; a success takes the keypoint for the later
 // points.  State flows only through one keyframe's mask, so the keyframes are independent: one
-// workgroup per (problem, keyframe).  It stages the keyframe's x, y and mask bits in LDS, lists the
-// keypoints by horizontal band (32 bands over the image height, a counting sort with ballot ranks, so
-// the list is in ascending keypoint index within a band), clears the keypoints
-// CreateInitialAssociations took (:314), and takes the points 256 at a time:
+// workgroup per (problem, keyframe).  It stages the keyframe's x, y and mask bits in LDS and lists
+// the keypoints by horizontal band (keyframe_take.hpp, shared with the cheap loop closure), clears
+// the keypoints CreateInitialAssociations took (:314), and takes the points 256 at a time:
 //   gate      one thread per point (newpoints_math.hpp project_gate); a refused point's record and
 //             verdict are final, the others are compacted in point order (ballot prefix);
-//   gather    64 surviving points at a time, 4 lanes per point: a scan of the bands the point's box
-//             touches (box, octave, available under the current mask, distance <= maxDist) into up
-//             to 8 candidates per point — a superset of what the point can ever be offered, since
-//             the mask only loses bits;
+//   gather    64 surviving points at a time, 4 lanes per point, up to 8 candidates per point;
 //   resolve   one wave takes the chunk's points in order with ordered_take.hpp's resolve_in_order
 //             (the resolver TrackLocalMap's matching uses; the argument for its exactness is there).
-//             A point with more than 8 candidates rescans its bands instead of reading its list.
 // The first build scanned all of the keyframe's keypoints per point (no index): 0.656 ms per launch
 // on the shape of tools/bench_new_points_assoc.py (256 problems x 8 keyframes x 2000 keypoints), the
 // ~nkp / 4 box tests per lane twice over (72 points are two rounds of 64) being nearly all of it.
-// The bands cut the scan to the ~8 % of the keypoints near the point's row; they are a counting sort
-// and not the 64-bit key sort of band_index.hpp, which would not fit beside the taker table in 64 KiB
-// of LDS.  Only commuting integer atomics, barriers and plain stores; nothing in the results depends
-// on the order in which threads run, and every loop is bounded by the counts.
+// The bands cut the scan to the ~8 % of the keypoints near the point's row.  Only commuting integer
+// atomics, barriers and plain stores; nothing in the results depends on the order in which threads
+// run, and every loop is bounded by the counts.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -32,8 +26,8 @@
 #include <vector>
 
 #include "common.hpp"
+#include "keyframe_take.hpp"
 #include "newpoints_math.hpp"
-#include "ordered_take.hpp"
 
 namespace mage {
 namespace {
@@ -43,18 +37,13 @@ using namespace newpoints;
 // The host-buffer entry's scratch slot, after newpoints.hip's (common.hpp stays as it is).
 constexpr ScratchSlot SCRATCH_NEWPOINTS_ASSOC = static_cast<ScratchSlot>(6);
 
-constexpr int NA_THREADS = 256;
-constexpr int NA_WAVES = NA_THREADS / kWave;
-constexpr int NA_CAP = 8;     // candidates kept per point (more: the point rescans its bands)
-constexpr int NA_GROUP = 4;   // lanes per point in the gather
-constexpr int NA_CHUNK = 64;  // points per gather + resolve round
-constexpr int NA_BANDS = 32;  // horizontal bands of the keypoint list
-constexpr int NA_BAD_OCT = 15;  // key octave of a keypoint no point can predict (predictions are 0..8)
-static_assert(NA_MAX_KP <= OT_MAX_TARGETS, "keypoint indices must fit resolve_in_order's packings");
+constexpr int NA_THREADS = kt::KT_THREADS;
+constexpr int NA_BANDS = kt::KT_BANDS;
+static_assert(NA_MAX_KP <= kt::KT_MAX_KP, "keypoint indices must fit resolve_in_order's packings");
 
 struct NaParams {
     AssocConsts c;
-    float band_scale;  // NA_BANDS / image height
+    kt::Search search;
     uint32_t kf_slots;
     const mage_new_point* points;
     uint32_t cap;
@@ -75,31 +64,6 @@ struct NaParams {
     uint32_t* status;
 };
 
-// The band of row y: monotone in y (a product with a positive constant, then a clamp), so every
-// keypoint with y0 <= y <= y1 lies in bands band_of(y0) .. band_of(y1).  NaN goes to band 0.
-__device__ __forceinline__ int band_of(float y, float scale)
-{
-    const float f = y * scale;
-    return f >= 0.f ? (f < (float)NA_BANDS ? (int)f : NA_BANDS - 1) : 0;
-}
-
-// The workgroup's LDS arrays.  The keyframe's Frame is declared beside them in the kernel: on its
-// own the compiler drops the members project_gate never reads (72 bytes).
-struct NaShared {
-    float x[NA_MAX_KP], y[NA_MAX_KP];
-    uint16_t key[NA_MAX_KP];  // by band, ascending keypoint within a band: octave << 12 | keypoint
-    int bstart[NA_BANDS + 1], brun[NA_BANDS];
-    int wband[NA_WAVES][NA_BANDS];
-    uint32_t m[NA_MAX_KP / 32];
-    int taker[NA_MAX_KP];
-    float px[NA_THREADS], py[NA_THREADS];
-    int pi[NA_THREADS];  // the surviving points: index, octave
-    signed char po[NA_THREADS];
-    uint32_t ent[NA_CHUNK][NA_CAP];  // kept_entry(keypoint, distance)
-    int n[NA_CHUNK];
-    uint32_t wsum[NA_WAVES];
-};
-
 // The workgroup's (problem, keyframe) pair.
 struct NaPair {
     uint32_t nkp, npts, nki;
@@ -114,63 +78,8 @@ struct NaPair {
     uint8_t* verdict;
 };
 
-// The keyframe in LDS and its keypoints listed by band.
-__device__ __forceinline__ void stage_keyframe(const NaParams& p, const NaPair& v, NaShared& s, Frame& frame,
-                                               long long pair)
-{
-    const int tid = threadIdx.x, lane = tid & 63;
-    if (tid < NA_BANDS) s.bstart[tid + 1] = 0;
-    if (tid == 0) s.bstart[0] = 0;
-    __syncthreads();
-    for (int i = tid; i < (int)v.nkp; i += NA_THREADS) {
-        const float y = v.kp[i].y;
-        s.x[i] = v.kp[i].x;
-        s.y[i] = y;
-        atomicAdd(&s.bstart[band_of(y, p.band_scale) + 1], 1);
-    }
-    for (int i = tid; i < NA_MAX_KP; i += NA_THREADS) s.taker[i] = OT_NO_TAKER;
-    for (int c0 = 0; c0 < NA_MAX_KP; c0 += NA_THREADS) {  // a wave's 64 mask bytes are two words (all 128 are written)
-        const int t = c0 + tid;
-        const unsigned long long bal = __ballot(t < (int)v.nkp && v.mask[t] != 0);
-        if (lane == 0) {
-            s.m[t >> 5] = (uint32_t)bal;
-            s.m[(t >> 5) + 1] = (uint32_t)(bal >> 32);
-        }
-    }
-    if (tid == 0) {
-        Frame f;
-        make_frame(p.kf_pos3 + 3 * pair, p.kf_r9 + 9 * pair, v.intr, f);
-        frame = f;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int acc = 0;
-        for (int b = 0; b < NA_BANDS; b++) {
-            s.brun[b] = acc;
-            acc += s.bstart[b + 1];
-            s.bstart[b + 1] = acc;
-        }
-    }
-    __syncthreads();
-    // the list: 256 keypoints at a time, each at its band's running base plus its rank among the
-    // band's keypoints of the chunk
-    for (int c0 = 0; c0 < (int)v.nkp; c0 += NA_THREADS) {
-        const int t = c0 + tid;
-        const int b = t < (int)v.nkp ? band_of(s.y[t], p.band_scale) : -1;
-        const int o = b >= 0 ? v.kp[t].octave : 0;  // in flight over the ballots
-        const int pos = rank_by_key<NA_WAVES>(b, true, NA_BANDS, s.brun, &s.wband[0][0], NA_BANDS);
-        int add = 0;
-        if (tid < NA_BANDS)
-            for (int w = 0; w < NA_WAVES; w++) add += s.wband[w][tid];
-        if (b >= 0) s.key[pos] = (uint16_t)((o >= 0 && o < NA_BAD_OCT ? o : NA_BAD_OCT) << 12 | t);
-        __syncthreads();  // wband and brun are read: the next chunk may write them
-        if (tid < NA_BANDS) s.brun[tid] += add;  // read again only after the next chunk's first barrier
-    }
-    __syncthreads();
-}
-
 // CreateInitialAssociations' own associations with this keyframe (:314) leave the mask.
-__device__ __forceinline__ void clear_claims(const NaPair& v, NaShared& s)
+__device__ __forceinline__ void clear_claims(const NaPair& v, kt::Shared& s)
 {
     if (v.slot >= 0)
         for (uint32_t i = threadIdx.x; i < v.npts; i += NA_THREADS) {
@@ -182,7 +91,7 @@ __device__ __forceinline__ void clear_claims(const NaPair& v, NaShared& s)
 
 // Points c0 .. c0 + 255, one thread each: a refused point's record and verdict are final, the others
 // are compacted in point order into px, py, pi, po.  Returns their count.
-__device__ __forceinline__ int gate_and_compact(const NaParams& p, const NaPair& v, NaShared& s, const Frame& frame,
+__device__ __forceinline__ int gate_and_compact(const NaParams& p, const NaPair& v, kt::Shared& s, const Frame& frame,
                                                 uint32_t c0)
 {
     const uint32_t i = c0 + threadIdx.x;
@@ -205,112 +114,11 @@ __device__ __forceinline__ int gate_and_compact(const NaParams& p, const NaPair&
             v.verdict[i * v.stride] = vd;
         }
     }
-    uint32_t cnt;
-    const uint32_t pos = block_prefix<NA_WAVES>(pass, s.wsum, &cnt);
-    if (pass) {
-        s.px[pos] = px;
-        s.py[pos] = py;
-        s.pi[pos] = (int)i;
-        s.po[pos] = (signed char)oc;
-    }
-    __syncthreads();
-    return (int)cnt;
-}
-
-// A surviving point's search: its box, its octave, its run of the band list, its descriptor.
-struct Box {
-    float x0, x1, y0, y1;
-    int qo, lo, hi;
-    uint4 a0, a1;
-};
-
-__device__ __forceinline__ Box load_box(const NaParams& p, const NaPair& v, const NaShared& s, int i)
-{
-    const float r = p.c.radius, qx = s.px[i], qy = s.py[i];
-    Box b;
-    b.x0 = qx - r, b.x1 = qx + r, b.y0 = qy - r, b.y1 = qy + r;
-    b.qo = s.po[i];
-    b.lo = s.bstart[band_of(b.y0, p.band_scale)];
-    b.hi = s.bstart[band_of(b.y1, p.band_scale) + 1];
-    const uint8_t* qd = v.kidesc + 32ll * v.pts[s.pi[i]].ki_index;
-    b.a0 = *reinterpret_cast<const uint4*>(qd);
-    b.a1 = *reinterpret_cast<const uint4*>(qd + 16);
-    return b;
-}
-
-// Entries lo + first, lo + first + step, ... of the box's run: `visit(t, d)` for every keypoint in
-// the box with the box's octave that is available under the current mask and within maxDist.
-template <typename F>
-__device__ __forceinline__ void scan(const NaParams& p, const NaPair& v, const NaShared& s, const Box& b, int first,
-                                     int step, F visit)
-{
-    for (int i = b.lo + first; i < b.hi; i += step) {
-        const int key = s.key[i], t = key & 0xFFF;
-        const float tx = s.x[t], ty = s.y[t];
-        if (!(tx >= b.x0 && tx <= b.x1 && ty >= b.y0 && ty <= b.y1) || (key >> 12) != b.qo || !mask_bit(s.m, t)) continue;
-        const int d = (int)hamming256(b.a0, b.a1, v.kdesc + 32ll * t);
-        if (d <= p.c.max_dist) visit(t, d);
-    }
-}
-
-// Surviving points s0 .. s0 + 63, 4 lanes per point walking the point's run 4 entries at a time: up
-// to 8 candidates per point into ent, their number into n.
-__device__ __forceinline__ void gather(const NaParams& p, const NaPair& v, NaShared& s, int s0, int cnt)
-{
-    const int j = threadIdx.x / NA_GROUP, sub = threadIdx.x % NA_GROUP;
-    const bool act = s0 + j < cnt;
-    Box b = {};
-    if (act) b = load_box(p, v, s, s0 + j);
-    int n = 0;
-    for (int i0 = b.lo; __any(i0 < b.hi); i0 += NA_GROUP) {
-        bool f = false;
-        uint32_t ent = 0;
-        if (i0 + sub < b.hi) {
-            Box one = b;  // this lane's entry alone
-            one.lo = i0 + sub;
-            one.hi = one.lo + 1;
-            scan(p, v, s, one, 0, 1, [&](int t, int d) {
-                f = true;
-                ent = kept_entry(t, d);
-            });
-        }
-        const int pos = group_append<NA_GROUP>(f, sub, n);
-        if (f && pos < NA_CAP) s.ent[j][pos] = ent;
-    }
-    if (act && sub == 0) s.n[j] = n;
-}
-
-// One wave: the chunk's cc points take their keypoints in order; every point's record and verdict.
-__device__ __forceinline__ void resolve(const NaParams& p, const NaPair& v, NaShared& s, int s0, int cc)
-{
-    resolve_in_order(
-        cc, p.c.max_dist, p.c.min_diff, s.m, s.taker,
-        [&](int j, bool act) {
-            const int n = act ? s.n[j] : 0;
-            Box b = {};
-            if (n > NA_CAP) b = load_box(p, v, s, s0 + j);
-            // every candidate of the lane that is still available (overflow: the bands rescanned)
-            return [=, &p, &v, &s](auto fn) {
-                if (n <= NA_CAP) {
-                    for (int e = 0; e < n; e++) {
-                        const uint32_t c = s.ent[j][e];
-                        if (mask_bit(s.m, kept_target(c))) fn(kept_target(c), kept_dist(c));
-                    }
-                } else {
-                    scan(p, v, s, b, 0, 1, fn);
-                }
-            };
-        },
-        [&](int j, bool ok, int t) {
-            const int i = s0 + j;
-            const long long o = (long long)s.pi[i] * v.stride;
-            v.out[o] = mage_new_point_assoc{s.px[i], s.py[i], s.po[i], ok ? t : -1};
-            v.verdict[o] = ok ? (uint8_t)NA_ASSOCIATED : (uint8_t)NA_NO_MATCH;
-        });
+    return kt::compact(s, pass, px, py, (int)i, oc);
 }
 
 // The taken keypoints (the claims included) back to the mask bytes.
-__device__ __forceinline__ void write_mask(const NaPair& v, const NaShared& s)
+__device__ __forceinline__ void write_mask(const NaPair& v, const kt::Shared& s)
 {
     for (int t = threadIdx.x; t < (int)v.nkp; t += NA_THREADS)
         if (!mask_bit(s.m, t)) v.mask[t] = 0;
@@ -318,8 +126,8 @@ __device__ __forceinline__ void write_mask(const NaPair& v, const NaShared& s)
 
 __global__ __launch_bounds__(NA_THREADS) void new_points_assoc_kernel(NaParams p)
 {
-    __shared__ NaShared s;
-    __shared__ Frame s_frame;
+    __shared__ kt::Shared s;
+    __shared__ Frame s_frame;  // beside the arrays: on its own the compiler drops the members project_gate never reads
     const int tid = threadIdx.x;
     const uint32_t prob = blockIdx.x / p.kf_slots, k = blockIdx.x % p.kf_slots;
     const long long pair = blockIdx.x;
@@ -345,16 +153,22 @@ __global__ __launch_bounds__(NA_THREADS) void new_points_assoc_kernel(NaParams p
     v.slot = p.kf_slot[pair];
     v.intr = p.kf_intr4 + 4 * pair;
 
-    stage_keyframe(p, v, s, s_frame, pair);
+    kt::stage_keyframe(
+        p.search.band_scale, (int)v.nkp, v.kp, s, [&](int t) { return v.mask[t] != 0; },
+        [&] {
+            Frame f;
+            make_frame(p.kf_pos3 + 3 * pair, p.kf_r9 + 9 * pair, v.intr, f);
+            s_frame = f;
+        });
     clear_claims(v, s);
+    const auto desc_of = [&](int i) { return v.kidesc + 32ll * v.pts[i].ki_index; };
     for (uint32_t c0 = 0; c0 < v.npts; c0 += NA_THREADS) {
         const int cnt = gate_and_compact(p, v, s, s_frame, c0);
-        for (int s0 = 0; s0 < cnt; s0 += NA_CHUNK) {
-            gather(p, v, s, s0, cnt);
-            __syncthreads();
-            if (tid < kWave) resolve(p, v, s, s0, min(NA_CHUNK, cnt - s0));
-            __syncthreads();
-        }
+        kt::take_in_order(p.search, v.kdesc, s, cnt, desc_of, [&](int i, bool ok, int t) {
+            const long long o = (long long)s.pi[i] * v.stride;
+            v.out[o] = mage_new_point_assoc{s.px[i], s.py[i], s.po[i], ok ? t : -1};
+            v.verdict[o] = ok ? (uint8_t)NA_ASSOCIATED : (uint8_t)NA_NO_MATCH;
+        });
     }
     write_mask(v, s);
 }
@@ -387,7 +201,7 @@ mage_status mage_new_points_associate_batch_device(
                  MAGE_EINVAL, "descriptor pointers must be 16-byte aligned");
     NaParams p{};
     p.c = newpoints::make_assoc_consts(*settings, *assoc);
-    p.band_scale = (float)NA_BANDS / p.c.image_h;
+    p.search = kt::Search{p.c.radius, (float)NA_BANDS / p.c.image_h, p.c.max_dist, p.c.min_diff};
     p.kf_slots = kf_slots;
     p.points = d_points;
     p.cap = cap;

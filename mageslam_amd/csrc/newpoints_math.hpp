@@ -8,6 +8,7 @@
 
 #include <math.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "../../include/mage_hot.h"
 
@@ -360,6 +361,40 @@ NP_HD uint8_t project_gate(const AssocConsts& c, const Frame& f, const float* in
     octave = compute_octave(sqrtf(d2), pt.d_min, c.log2s);
     if (octave < 0 || octave > c.num_levels) return NA_OCTAVE;
     return NA_NO_MATCH;
+}
+
+// The host twins' descriptor search (newpoints.cpp, loopclose.cpp).
+inline int host_hamming256(const uint8_t* a, const uint8_t* b)
+{
+    int d = 0;
+    for (int i = 0; i < 4; i++) {
+        uint64_t x, y;
+        memcpy(&x, a + 8 * i, 8);
+        memcpy(&y, b + 8 * i, 8);
+        d += __builtin_popcountll(x ^ y);
+    }
+    return d;
+}
+
+// The single-query RadiusMatch (FeatureMatcher.cpp:386-446) against the available keypoints, the
+// candidates in ascending keypoint index: the keypoint, or -1.
+inline int host_radius_match_one(const AssocConsts& c, float px, float py, int octave, const uint8_t* desc,
+                                 const mage_keypoint* kp, const uint8_t* kdesc, uint32_t n, const uint8_t* mask)
+{
+    const float r = c.radius;
+    int best = c.max_dist + 1, second = 2147483647, train = -1;
+    for (uint32_t t = 0; t < n; t++) {
+        const float tx = kp[t].x, ty = kp[t].y;
+        if (!(tx >= px - r && tx <= px + r && ty >= py - r && ty <= py + r) || kp[t].octave != octave || !mask[t])
+            continue;
+        const int d = host_hamming256(desc, kdesc + 32ull * t);
+        if (d < best) {
+            train = (int)t;
+            second = best;
+            best = d;
+        }
+    }
+    return train != -1 && second - best > c.min_diff ? train : -1;
 }
 
 }  // namespace newpoints
