@@ -8,7 +8,8 @@
 //      per instruction), then a dword-vectorised strict 3x3 NMS, border filter, per-tile LDS
 //      compaction, one global atomic per tile.  Candidates are packed u32 (y<<20 | x<<8 | score).
 //   2. select_kernel    grid (B), 1024 threads: 256-bin histogram -> RetainBestFeatures cut,
-//      bbox, 32x32 cell counting sort, per-item ANMS ring search, 64-bit key bitonic sort
+//      bbox, 32x32 cell counting sort, per-item ANMS search of the cells within the suppression
+//      radius, 64-bit key bitonic sort
 //      (registers / wave shuffles / LDS by stride),
 //      emits keypoints in canonical order (ANMS rank r desc, strength desc, raster asc).
 //   3. describe_kernel  grid (cap/4, B), one wave per keypoint: raw window -> separable 8U
@@ -1043,6 +1044,18 @@ __device__ __forceinline__ int cand_x(uint32_t c) { return (int)((c >> 8) & 0xFF
 __device__ __forceinline__ int cand_y(uint32_t c) { return (int)(c >> 20); }
 __device__ __forceinline__ int cand_s(uint32_t c) { return (int)(c & 0xFFu); }
 
+// d * n / den for 0 <= d < den <= 4096, n <= CELLMAX (the cell of a coordinate d pixels into the
+// bounding box) without an integer division: d * n < 2^24 is exact in f32 and the quotient is below
+// n, so the product with inv = 1 / den is within 2^-10 of it and one integer correction step either
+// way makes it the exact floor.
+__device__ __forceinline__ int cell_of(int d, int n, int den, float inv)
+{
+    const int num = __mul24(d, n);
+    int q = (int)__fmul_rn((float)num, inv);
+    const int rem = num - __mul24(q, den);
+    return q + (rem >= den) - (rem < 0);
+}
+
 static_assert(SEL_THREADS == SORT_THREADS, "select_kernel sorts with the shared LDS sort");
 
 #ifndef MAGE_SELECT_STAMPS
@@ -1070,7 +1083,7 @@ __device__ __forceinline__ void select_frame(int f, int G, const uint32_t* __res
     __shared__ uint32_t sorted[KMAX];
     __shared__ uint32_t cellStart[CELLMAX + 1];
     __shared__ unsigned long long keys[KMAX];
-    __shared__ int s_cut, s_K, s_minX, s_maxX, s_minY, s_maxY, s_minS, s_gmax, s_mcd2, s_mode;
+    __shared__ int s_cut, s_K, s_minX, s_maxX, s_minY, s_maxY, s_minS, s_gmax, s_rad, s_mode;
     __shared__ float s_rob, s_robInv;
 
     const int tid = threadIdx.x;
@@ -1277,15 +1290,27 @@ __device__ __forceinline__ void select_frame(int f, int G, const uint32_t* __res
             float rob = __fsub_rn(p.max_r, __fmul_rn(__fdiv_rn(val, (float)(p.strong - t)), range));
             s_rob = rob;
             s_robInv = __fdiv_rn(1.0f, rob);
-            s_gmax = (int)(((double)(maxX - minX)) * ((double)(maxY - minY)) / (double)N);
-            int dx = max((maxX - minX) / numX, 1), dy = max((maxY - minY) / numY, 1);
-            s_mcd2 = min(dx, dy) * min(dx, dy);
+            const int gmax = (int)(((double)(maxX - minX)) * ((double)(maxY - minY)) / (double)N);
+            s_gmax = gmax;
+            // search radius: the largest r with r^2 < gmax (none, -1, when gmax <= 0); a float
+            // estimate made exact by integer compares
+            long long r = -1;
+            if (gmax > 0) {
+                r = (long long)sqrtf((float)gmax);
+                while (r * r >= gmax) r--;
+                while ((r + 1) * (r + 1) < gmax) r++;
+            }
+            // a bounding box narrower than the grid, cells thinner than a pixel (below): -2
+            const bool thin = (maxX - minX) / numX == 0 || (maxY - minY) / numY == 0;
+            s_rad = thin ? -2 : (int)r;
         }
         // counting sort by cell
+        const int spanX = maxX + 1 - minX, spanY = maxY + 1 - minY;
+        const float invX = __fdiv_rn(1.0f, (float)spanX), invY = __fdiv_rn(1.0f, (float)spanY);
         for (int i = tid; i < K; i += SEL_THREADS) {
             uint32_t c = items[i];
-            int cx = (cand_x(c) - minX) * numX / (maxX + 1 - minX);
-            int cy = (cand_y(c) - minY) * numY / (maxY + 1 - minY);
+            int cx = cell_of(cand_x(c) - minX, numX, spanX, invX);
+            int cy = cell_of(cand_y(c) - minY, numY, spanY, invY);
             atomicAdd(&cellStart[cy * numX + cx + 1], 1u);
         }
         __syncthreads();
@@ -1312,25 +1337,31 @@ __device__ __forceinline__ void select_frame(int f, int G, const uint32_t* __res
         __syncthreads();
         for (int i = tid; i < K; i += SEL_THREADS) {
             uint32_t c = items[i];
-            int cx = (cand_x(c) - minX) * numX / (maxX + 1 - minX);
-            int cy = (cand_y(c) - minY) * numY / (maxY + 1 - minY);
+            int cx = cell_of(cand_x(c) - minX, numX, spanX, invX);
+            int cy = cell_of(cand_y(c) - minY, numY, spanY, invY);
             uint32_t pos = atomicAdd(&fill[cy * numX + cx], 1u);
             sorted[pos] = c;
         }
         __syncthreads();
         SEL_STAMP(7);
         const float rob = s_rob, robInv = s_robInv;
-        const int gmax = s_gmax, mcd2 = s_mcd2;
+        const int gmax = s_gmax, rad = s_rad;
         // Ring search (OpenCVModified.cpp:266-326).  Its result is min(gmax, d^2 to the nearest
-        // stronger item): an item in ring d is at least (d - 1) cells of side >= sqrt(mcd2) away,
-        // so the rings it stops before cannot lower minR2.  Every ring it can visit lies within
-        // D - 1 of the item's cell, D the first ring with max(0, D - 1)^2 mcd2 >= gmax; for small D
-        // the (2D - 1)^2 square is searched row by row (a row's cells are one contiguous run of
-        // the cell-sorted items) without the ring loop's per-cell bookkeeping, and items are taken
-        // in cell order so neighbouring lanes read the same runs.
-        int D = 0;
-        while (max(0, D - 1) * max(0, D - 1) * mcd2 < gmax && D < 5) D++;
-        const bool square = max(0, D - 1) * max(0, D - 1) * mcd2 >= gmax;
+        // stronger item): an item in ring d is at least (d - 1) cells of side >= sqrt(mcd2) away
+        // (mcd2 the reference's squared minimum cell side), so the rings it stops before cannot
+        // lower minR2.  Only items with d^2 < gmax can matter: |dx| <= rad and |dy| <= rad, rad the
+        // largest integer with rad^2 < gmax.  The cell index is monotone in the coordinate, so
+        // those items lie in the cells [cell(x - rad), cell(x + rad)] x [cell(y - rad), cell(y +
+        // rad)] (coordinates clamped to the bounding box), whatever the cell size: about
+        // K (2 rad + cell side)^2 / area items, 16 on C2, where the (2D - 1)^2 square of whole
+        // rings held 23 (D = 2) or 60 (D = 3).  The box is searched row by row (a row's cells are
+        // one contiguous run of the cell-sorted items), and items are taken in cell order so
+        // neighbouring lanes read the same runs.  With gmax <= 0 (rad = -1) nothing is visited.
+        // The argument needs cells of at least sqrt(mcd2) pixels.  The reference takes mcd2 from
+        // max(extent / cells, 1), so over a bounding box narrower than the grid (thin) its cells
+        // are thinner than the pixel it assumes, its loop can stop before a nearer stronger item
+        // and its result is what its ring order gives: those frames walk the rings as it does.
+        const bool thin = rad == -2;
         unsigned long long mykeys[KMAX / SEL_THREADS];
 #pragma unroll
         for (int q = 0; q < KMAX / SEL_THREADS; q++) {
@@ -1339,15 +1370,38 @@ __device__ __forceinline__ void select_frame(int f, int G, const uint32_t* __res
             if (i < K) {
                 uint32_t c = sorted[i];
                 const int x = cand_x(c), y = cand_y(c), s = cand_s(c);
-                const int cx = (x - minX) * numX / (maxX + 1 - minX);
-                const int cy = (y - minY) * numY / (maxY + 1 - minY);
                 const float strength = (float)s;
                 const float sth = strength >= 0 ? __fadd_rn(__fmul_rn(strength, rob), 0.002f)
                                                  : __fadd_rn(__fmul_rn(strength, robInv), 0.002f);
                 int minR2 = gmax;
-                if (square) {
-                    const int x0 = max(cx - (D - 1), 0), x1 = min(cx + (D - 1), numX - 1);
-                    const int y0 = max(cy - (D - 1), 0), y1 = min(cy + (D - 1), numY - 1);
+                if (thin) {
+                    const int cx = cell_of(x - minX, numX, spanX, invX), cy = cell_of(y - minY, numY, spanY, invY);
+                    for (int d = 0; max(0, d - 1) * max(0, d - 1) < minR2; d++) {  // mcd2 = 1 here
+                        for (int yy = -d; yy <= d; yy++) {
+                            const int cYY = cy + yy;
+                            if (cYY < 0 || cYY >= numY) continue;
+                            const bool edgeRow = (yy == -d || yy == d);
+                            const int step = edgeRow ? 1 : max(2 * d, 1);
+                            for (int xx = -d; xx <= d; xx += step) {
+                                const int cXX = cx + xx;
+                                if (cXX < 0 || cXX >= numX) continue;
+                                const int cell = cYY * numX + cXX;
+                                const uint32_t e = cellStart[cell + 1];
+                                for (uint32_t qq = cellStart[cell]; qq < e; qq++) {
+                                    uint32_t o = sorted[qq];
+                                    if ((float)cand_s(o) > sth) {
+                                        int ddx = x - cand_x(o), ddy = y - cand_y(o);
+                                        minR2 = min(minR2, ddx * ddx + ddy * ddy);
+                                    }
+                                }
+                            }
+                        }
+                    }
+                } else if (rad >= 0) {
+                    const int x0 = cell_of(max(x - rad, minX) - minX, numX, spanX, invX);
+                    const int x1 = cell_of(min(x + rad, maxX) - minX, numX, spanX, invX);
+                    const int y0 = cell_of(max(y - rad, minY) - minY, numY, spanY, invY);
+                    const int y1 = cell_of(min(y + rad, maxY) - minY, numY, spanY, invY);
                     // (float)s > sth for an integer s in [0, 255]: s >= floor(sth) + 1 (no conversion
                     // per visited item; a branch-free select and one LDS atomic per wave for the
                     // item / key appends measured 1-2 % slower)
@@ -1369,28 +1423,6 @@ __device__ __forceinline__ void select_frame(int f, int G, const uint32_t* __res
                             visit(o3);
                         }
                         for (; qq < e; qq++) visit(sorted[qq]);
-                    }
-                } else {
-                    for (int d = 0; max(0, d - 1) * max(0, d - 1) * mcd2 < minR2; d++) {
-                        for (int yy = -d; yy <= d; yy++) {
-                            const int cYY = cy + yy;
-                            if (cYY < 0 || cYY >= numY) continue;
-                            const bool edgeRow = (yy == -d || yy == d);
-                            const int step = edgeRow ? 1 : max(2 * d, 1);
-                            for (int xx = -d; xx <= d; xx += step) {
-                                const int cXX = cx + xx;
-                                if (cXX < 0 || cXX >= numX) continue;
-                                const int cell = cYY * numX + cXX;
-                                const uint32_t e = cellStart[cell + 1];
-                                for (uint32_t qq = cellStart[cell]; qq < e; qq++) {
-                                    uint32_t o = sorted[qq];
-                                    if ((float)cand_s(o) > sth) {
-                                        int ddx = x - cand_x(o), ddy = y - cand_y(o);
-                                        minR2 = min(minR2, ddx * ddx + ddy * ddy);
-                                    }
-                                }
-                            }
-                        }
                     }
                 }
                 uint32_t raster = (uint32_t)y * (uint32_t)p.w + (uint32_t)x;

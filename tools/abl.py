@@ -3,11 +3,15 @@ the product).
 
   python tools/abl.py build <source.hip> name:DEF=1+DEF2=3 [name:...]   # here (CPU): abl/<name>/libmage_hot.so
   python tools/abl.py run name[,name...]                                # on the GPU box
+  python tools/abl.py extract name[,name...]                            # on the GPU box: extraction alone
 
 `run` extracts + matches one 256-frame C2 batch per iteration (as bench.py's step does), prints each
 variant's per-kernel average launch time (the library's dispatch timestamps) and a checksum of the
 keypoints, descriptors and matches, which must agree between variants of the same algorithm.
 MAGE_ABLATE_GATE=<g> forces the FAST candidate gate of every timed batch.
+`run` extracts B + 1 = 257 frames per step (the matcher pairs each frame with its predecessor), so
+select_kernel, one workgroup per CU, runs its 257th workgroup in a second round there; `extract`
+times the extraction of a 256-frame batch alone, the shape of bench.py's step.
 
 The fp4 matcher's tile pipeline against the parent commit (profiles/r9_match_pipe.md):
   python tools/abl.py build mageslam_amd/csrc/match.hip parent@HEAD pipe1:MAGE_FP4_PIPE=1 pipe0:MAGE_FP4_PIPE=0
@@ -82,30 +86,32 @@ def build(src, specs):
         print("built", out, flags, flush=True)
 
 
-def run(names):
+def run(names, match=True):
     import torch
     sys.path.insert(0, str(ROOT))
     from mageslam_amd import _lib, matcher, orb, synth
     W, H, B, N = 1280, 720, 256, 2000
     gate = int(os.environ["MAGE_ABLATE_GATE"]) if os.environ.get("MAGE_ABLATE_GATE") else None
-    frames = torch.empty((B + 1, H, W), dtype=torch.uint8, device="cuda")
-    kp = torch.zeros((B + 1, N * 28), dtype=torch.uint8, device="cuda")
-    desc = torch.zeros((B + 1, N, 32), dtype=torch.uint8, device="cuda")
-    cnt = torch.zeros(B + 1, dtype=torch.int32, device="cuda")
+    F = B + 1 if match else B
+    frames = torch.empty((F, H, W), dtype=torch.uint8, device="cuda")
+    kp = torch.zeros((F, N * 28), dtype=torch.uint8, device="cuda")
+    desc = torch.zeros((F, N, 32), dtype=torch.uint8, device="cuda")
+    cnt = torch.zeros(F, dtype=torch.int32, device="cuda")
     mt = torch.zeros((B, N * 16), dtype=torch.uint8, device="cuda")
     nm = torch.zeros(B, dtype=torch.int32, device="cuda")
     for v in names:
         L = C.CDLL(str(ROOT / "abl" / v / "libmage_hot.so"))
         _lib._declare(L)
         _lib._lib = L
-        orb.synth_frames_device(frames, B + 1, W, H, 0, synth.FRAME_SEED)
+        orb.synth_frames_device(frames, F, W, H, 0, synth.FRAME_SEED)
         det = orb.OrbDetector(nfeatures=N)
 
         def step():
             if gate is not None:
                 det.set_fast_gate(gate)
             det.detect_and_compute_batch_device(frames, W, H, kp, desc, cnt, N)
-            matcher.match_batch_device(desc[1:], N * 32, cnt[1:], desc[:-1], N * 32, cnt[:-1], B, 30, 1, mt, N, nm)
+            if match:
+                matcher.match_batch_device(desc[1:], N * 32, cnt[1:], desc[:-1], N * 32, cnt[:-1], B, 30, 1, mt, N, nm)
 
         for _ in range(3):
             step()
@@ -118,13 +124,14 @@ def run(names):
         rep = _lib.profile_report()
         L.mage_profile_enable(0)
         h = hashlib.sha256()
-        for t in (kp, desc, cnt, nm):
+        for t in (kp, desc, cnt) + ((nm,) if match else ()):
             h.update(t.cpu().numpy().tobytes())
         mtn = mt.cpu().numpy()
-        for b in range(B):
+        for b in range(B if match else 0):
             h.update(mtn[b, : 16 * int(nm[b])].tobytes())
         ks = " ".join(f"{k} {ms / c:.4f}" for k, (c, ms) in sorted(rep.items()))
-        print(f"{v:>10}: {ks}  | sha {h.hexdigest()[:12]} matches/frame {nm.float().mean().item():.1f}", flush=True)
+        tail = f" matches/frame {nm.float().mean().item():.1f}" if match else ""
+        print(f"{v:>10}: {ks}  | sha {h.hexdigest()[:12]}{tail}", flush=True)
         det.close()
 
 
@@ -132,4 +139,4 @@ if __name__ == "__main__":
     if sys.argv[1] == "build":
         build(sys.argv[2], sys.argv[3:])
     else:
-        run(sys.argv[2].split(","))
+        run(sys.argv[2].split(","), match=sys.argv[1] != "extract")
