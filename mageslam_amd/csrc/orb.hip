@@ -1745,11 +1745,56 @@ __device__ __forceinline__ void static_for(F&& f)
 // lines touched drop from 10 to 5 for the ~55 % of windows inside one 32-byte brick column.
 // LDS rows have an odd number of 16-byte parts, so the 4-5 dwords a row's tests read start 4
 // banks apart for 8 consecutive rows (tests bank as (a / 4) mod 32).
-template <int RB, bool MULTI, int KP>
+//
+// Per-wave work hoisted out of the keypoint loop (profiles/r11_describe.md; each piece has a
+// compile-time switch so tools/abl.py can time it alone):
+#ifndef MAGE_DESC_TRANDOM
+#define MAGE_DESC_TRANDOM 1  // the random pattern is the template parameter RANDOM, not the runtime p.random: the
+                             // other instantiations hold no pattern_rotation (f64 sin / cos) and keep e[] loop-invariant
+#endif
+#ifndef MAGE_DESC_HOIST
+#define MAGE_DESC_HOIST 0  // !MULTI && !RANDOM: the lane's 8 LDS offsets written out once per wave; a read is offset + window
+                           // base + phase.  Off: with RANDOM a template parameter the compiler hoists them itself (C2: 285
+                           // static VALU without, 293 with; describe 0.0593-0.0610 ms without, 0.0595-0.0606 with)
+#endif
+#ifndef MAGE_DESC_ONESTORE
+#define MAGE_DESC_ONESTORE 1  // ballot word c of keypoint q into lane 4q + c; one masked 8-byte store per wave
+#endif
+#ifndef MAGE_DESC_XYONCE
+#define MAGE_DESC_XYONCE 1  // the wave's KP keypoint records by scalar loads, once, for staging and phases
+#endif
+static_assert(!MAGE_DESC_HOIST || MAGE_DESC_TRANDOM, "hoisted offsets need the random pattern known at compile time");
+
+// Lanes L0 .. L0 + 3 of the pair (hi, lo) = the wave-uniform 64-bit words m[0 .. 3] (this clang
+// has no writelane builtin).  m[] are ballots, i.e. SGPR pairs written by VALU compares that the
+// compiler may place directly ahead of the statement, and it pads nothing inside one: gfx90a and
+// later (gfx950 too) need 2 wait states between a VALU write of an SGPR / VCC and a VALU that
+// reads it as a source operand (LLVM's VALUWriteSGPRVALURead; hipcc emits `s_nop 1` for it), which
+// the leading s_nop 1 supplies.  The lane select is an immediate, so the 4-state rule for an SGPR
+// lane select does not apply.
+template <int L0>
+__device__ __forceinline__ void write_lanes4(uint32_t& lo, uint32_t& hi, const unsigned long long (&m)[4])
+{
+    asm("s_nop 1\n\t"
+        "v_writelane_b32 %0, %2, %10\n\tv_writelane_b32 %1, %3, %10\n\t"
+        "v_writelane_b32 %0, %4, %11\n\tv_writelane_b32 %1, %5, %11\n\t"
+        "v_writelane_b32 %0, %6, %12\n\tv_writelane_b32 %1, %7, %12\n\t"
+        "v_writelane_b32 %0, %8, %13\n\tv_writelane_b32 %1, %9, %13"
+        : "+v"(lo), "+v"(hi)
+        : "s"((uint32_t)m[0]), "s"((uint32_t)(m[0] >> 32)), "s"((uint32_t)m[1]), "s"((uint32_t)(m[1] >> 32)),
+          "s"((uint32_t)m[2]), "s"((uint32_t)(m[2] >> 32)), "s"((uint32_t)m[3]), "s"((uint32_t)(m[3] >> 32)),
+          "i"(L0), "i"(L0 + 1), "i"(L0 + 2), "i"(L0 + 3));
+}
+
+template <int RB, bool MULTI, int KP, bool RANDOM>
 __global__ __launch_bounds__(DESC_WAVES * kWave) void describe_blurred_kernel(
     DescParams p, const uint32_t* __restrict__ xy_in, const uint32_t* __restrict__ n_in,
     const int8_t* __restrict__ pattern, uint8_t* __restrict__ desc_out)
 {
+    static_assert(MAGE_DESC_TRANDOM || !RANDOM, "without the switch the host passes p.random");
+    static_assert(4 * KP <= kWave, "one descriptor word per lane");
+    constexpr bool HOIST = MAGE_DESC_HOIST && !MULTI && !RANDOM;
+    constexpr bool ONESTORE = MAGE_DESC_ONESTORE != 0, XYONCE = MAGE_DESC_XYONCE != 0;
     constexpr int BDMAX = 2 * RB + 1;
     constexpr int NP = (BDMAX + 30) / 16;  // 16-byte parts per window row (any column phase)
     constexpr int NI = BDMAX * NP;         // 16-byte items per keypoint
@@ -1767,6 +1812,12 @@ __global__ __launch_bounds__(DESC_WAVES * kWave) void describe_blurred_kernel(
     const int n = (int)n_in[f];
     if (k0 >= n) return;
     const int R = p.R;
+    const bool random = MAGE_DESC_TRANDOM ? RANDOM : p.random != 0;
+    // the wave's keypoint records (k0 is wave-uniform: scalar loads), clamped to the frame's last
+    uint32_t xyq[KP];
+    if constexpr (XYONCE)
+#pragma unroll
+        for (int q = 0; q < KP; q++) xyq[q] = xy_in[(long long)f * p.out_cap + min(k0 + q, n - 1)];
     // the tests' pattern rows, issued ahead of the window loads so both round trips overlap
     // (without orientation the wave's keypoints share one set; the per-keypoint loads of the
     // loop below had left each of its 4 chunks waiting on an L2 round trip of its own)
@@ -1778,11 +1829,11 @@ __global__ __launch_bounds__(DESC_WAVES * kWave) void describe_blurred_kernel(
     for (int q = 0; q < NE; q++) {
         const long long ki = (long long)f * p.out_cap + min(k0 + q, n - 1);
         const int rot = MULTI ? (p.lvl[ki] & 0xFF) : 0;
-        const char4* pr = pat + (p.random ? 0 : rot * 256);  // cvRound(angle / 12) % 30 (:526)
+        const char4* pr = pat + (random ? 0 : rot * 256);  // cvRound(angle / 12) % 30 (:526)
 #pragma unroll
         for (int c = 0; c < 4; c++) e[q][c] = pr[c * kWave + lane];  // (x0, y0, x1, y1) of bit 64*c + lane
     }
-    if (p.random)
+    if (random)
 #pragma unroll
         for (int q = 0; q < KP; q++) ang[q] = p.kp_angle[7 * ((long long)f * p.out_cap + min(k0 + q, n - 1))];
     // load slot j: keypoint q, item i = row i / NP, part i % NP; keypoints keep the pattern
@@ -1797,16 +1848,24 @@ __global__ __launch_bounds__(DESC_WAVES * kWave) void describe_blurred_kernel(
         const int i = PAIR ? (lane & 31) : lane + kWave * (j % NLDC);
         const long long ki = (long long)f * p.out_cap + min(k0 + q, n - 1);
         const int l = MULTI ? (__builtin_amdgcn_readfirstlane(p.lvl[ki]) >> 8) : 0;  // wave-uniform (no PAIR)
-        const uint32_t xy = xy_in[ki];
+        uint32_t xy;
+        if constexpr (!XYONCE) xy = xy_in[ki];
+        else if constexpr (PAIR) xy = lane >> 5 ? xyq[2 * j + 1] : xyq[2 * j];
+        else xy = xyq[j / NLDC];
         const uint8_t* src = p.lev.base[l] + (long long)f * p.lev.pitch[l];
         const int bcols = p.lev.stride[l], brows = (p.lh[MULTI ? l : 0] + 3) >> 2;
         const int x0 = (int)(xy & 0xFFFFu) - R, y0 = (int)(xy >> 16) - R;
         const int r = i / NP, pt = i - r * NP;
         const int gy = min(max(y0 + r, 0), 4 * brows - 1);
         const int gx = min(max((x0 & ~15) + 16 * pt, 0), 32 * bcols - 16);
-        if (i < NI)
-            v[j] = *reinterpret_cast<const u32x4*>(src + ((long long)(gy >> 2) * bcols + (gx >> 5)) * 128 +
-                                                   (gy & 3) * 32 + (gx & 31));
+        if (i < NI) {
+            if constexpr (XYONCE && !MULTI)  // one level: a scalar frame base + the lane's 32-bit offset (a level is < 2^31 bytes)
+                v[j] = *reinterpret_cast<const u32x4*>(src + (((uint32_t)(gy >> 2) * bcols + (gx >> 5)) * 128u +
+                                                              (gy & 3) * 32 + (gx & 31)));
+            else
+                v[j] = *reinterpret_cast<const u32x4*>(src + ((long long)(gy >> 2) * bcols + (gx >> 5)) * 128 +
+                                                       (gy & 3) * 32 + (gx & 31));
+        }
     });
     static_for<NSLOT>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
@@ -1816,37 +1875,67 @@ __global__ __launch_bounds__(DESC_WAVES * kWave) void describe_blurred_kernel(
         if (i < NI) *reinterpret_cast<u32x4*>(&win[wave][q][r * WPC + 16 * pt]) = v[j];
     });
     wave_lds_sync();
+    // HOIST: the wave's keypoints share the pattern, so the lane's offsets into a window are
+    // computed here once; a read below adds the window's base and column phase, both scalar
+    int o0[4], o1[4];
+    if constexpr (HOIST)
 #pragma unroll
-    for (int q = 0; q < KP; q++) {
+        for (int c = 0; c < 4; c++) {
+            o0[c] = (R + e[0][c].y) * WPC + R + e[0][c].x;
+            o1[c] = (R + e[0][c].w) * WPC + R + e[0][c].z;
+        }
+    uint32_t dlo = 0, dhi = 0;  // ONESTORE: lane 4q + c holds word c of keypoint q
+    static_for<KP>([&](auto qc) {
+        constexpr int q = decltype(qc)::value;
         const int k = k0 + q;
-        if (k >= n) break;
+        if (k >= n) return;
         const long long ki = (long long)f * p.out_cap + k;
-        const uint32_t xy = xy_in[ki];
+        const uint32_t xy = XYONCE ? xyq[q] : xy_in[ki];
         const uint8_t* wb = &win[wave][q][((int)(xy & 0xFFFFu) - R) & 15];  // (x0 & 15): the window's column phase
-        char4 eq[4];
-#pragma unroll
-        for (int c = 0; c < 4; c++) eq[c] = e[MULTI ? q : 0][c];
-        if (p.random) {  // random pattern: rotation by the keypoint angle
-            float ra, rb_;
-            pattern_rotation(ang[q], ra, rb_);
-#pragma unroll
-            for (int c = 0; c < 4; c++) eq[c] = rotate_test(eq[c], ra, rb_);
-        }
         int t0[4], t1[4];
+        if constexpr (HOIST) {
 #pragma unroll
-        for (int c = 0; c < 4; c++) {
-            t0[c] = wb[(R + eq[c].y) * WPC + R + eq[c].x];
-            t1[c] = wb[(R + eq[c].w) * WPC + R + eq[c].z];
-        }
-        // lane c stores the descriptor's 64-bit word c
-        unsigned long long mw = 0;
+            for (int c = 0; c < 4; c++) {
+                t0[c] = wb[o0[c]];
+                t1[c] = wb[o1[c]];
+            }
+        } else {
+            char4 eq[4];
 #pragma unroll
-        for (int c = 0; c < 4; c++) {
-            const unsigned long long m = __ballot(t0[c] < t1[c]);
-            mw = lane == c ? m : mw;
+            for (int c = 0; c < 4; c++) eq[c] = e[MULTI ? q : 0][c];
+            if (random) {  // random pattern: rotation by the keypoint angle
+                float ra, rb_;
+                pattern_rotation(ang[q], ra, rb_);
+#pragma unroll
+                for (int c = 0; c < 4; c++) eq[c] = rotate_test(eq[c], ra, rb_);
+            }
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                t0[c] = wb[(R + eq[c].y) * WPC + R + eq[c].x];
+                t1[c] = wb[(R + eq[c].w) * WPC + R + eq[c].z];
+            }
         }
-        if (lane < 4) reinterpret_cast<unsigned long long*>(desc_out + ki * 32)[lane] = mw;
-    }
+        if constexpr (ONESTORE) {
+            unsigned long long m[4];
+#pragma unroll
+            for (int c = 0; c < 4; c++) m[c] = __ballot(t0[c] < t1[c]);
+            write_lanes4<4 * q>(dlo, dhi, m);
+        } else {
+            // lane c stores the descriptor's 64-bit word c
+            unsigned long long mw = 0;
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                const unsigned long long m = __ballot(t0[c] < t1[c]);
+                mw = lane == c ? m : mw;
+            }
+            if (lane < 4) reinterpret_cast<unsigned long long*>(desc_out + ki * 32)[lane] = mw;
+        }
+    });
+    // the wave's min(KP, n - k0) descriptors are contiguous: 8 bytes per lane, none past keypoint n - 1
+    if constexpr (ONESTORE)
+        if (lane < 4 * min(KP, n - k0))
+            reinterpret_cast<unsigned long long*>(desc_out + ((long long)f * p.out_cap + k0) * 32)[lane] =
+                (unsigned long long)dhi << 32 | dlo;
 }
 // Whole-brick windows (MAGE_DESC_COMPACT=0): MULTI = false (one level, no orientation: the
 // default configuration): level 0 and rotation 0 without the per-keypoint level lookups.
@@ -2924,10 +3013,18 @@ mage_status run_batch(OrbDetector* o, const uint8_t* d_frames, uint32_t batch, i
                 dp.chunks = (int)((cap + DESC_WAVES * kp - 1) / (DESC_WAVES * kp));
                 dp.frames = (int)batch;
                 const dim3 g3((unsigned)(dp.chunks * ((batch + 7) / 8) * 8), 1, 1);
-                auto kern = multi ? (dp.R <= 7 ? describe_blurred_kernel<7, true, KPW>
-                                               : (dp.R <= 13 ? describe_blurred_kernel<13, true, KPW> : describe_blurred_kernel<RMAX, true, MAGE_DESC_KP_WIDE>))
-                                  : (dp.R <= 7 ? describe_blurred_kernel<7, false, KPW7>
-                                               : (dp.R <= 13 ? describe_blurred_kernel<13, false, KPW> : describe_blurred_kernel<RMAX, false, MAGE_DESC_KP_WIDE>));
+                // one level: the kernel adds 32-bit lane offsets to the frame's base
+                MAGE_REQUIRE(multi || g.lv[0].bpitch < (1ll << 32), MAGE_EUNSUPPORTED, "a blurred frame of 4 GiB or more");
+                auto pick = [&](auto rnd) {
+                    constexpr bool RND = decltype(rnd)::value;
+                    return multi ? (dp.R <= 7 ? describe_blurred_kernel<7, true, KPW, RND>
+                                              : (dp.R <= 13 ? describe_blurred_kernel<13, true, KPW, RND>
+                                                            : describe_blurred_kernel<RMAX, true, MAGE_DESC_KP_WIDE, RND>))
+                                 : (dp.R <= 7 ? describe_blurred_kernel<7, false, KPW7, RND>
+                                              : (dp.R <= 13 ? describe_blurred_kernel<13, false, KPW, RND>
+                                                            : describe_blurred_kernel<RMAX, false, MAGE_DESC_KP_WIDE, RND>));
+                };
+                auto kern = MAGE_DESC_TRANDOM && dp.random ? pick(std::bool_constant<MAGE_DESC_TRANDOM != 0>{}) : pick(std::false_type{});
                 launch("orb.describe", kern, g3, dim3(DESC_WAVES * kWave), 0, st, dp, (const uint32_t*)o->xy.as<uint32_t>(),
                        d_n, (const int8_t*)o->pattern.as<int8_t>(), d_desc);
             } else {
